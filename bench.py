@@ -1,20 +1,27 @@
 #!/usr/bin/env python
 """bench.py -- training images/sec of the MNIST-32 CNN-VAE + GaussianPrior step on MI355X (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One step = forward + backward + (RCCL all-reduce of the flat gradient buffer when N > 1) + Adam over one resident
 synthetic batch of 1024 images per GPU (weak scaling), replayed as a hipGraph, plus the latent statistics update
 (GaussianModel.update, the streaming fp64 covariance the Gaussian-W2 path consumes).  Inputs are already in HBM when
-the timed region starts.  Rank 0 prints ONE JSON line.
+the timed region starts, and are the same from run to run.  Rank 0 prints ONE JSON line; `ms_per_step` is the wall
+time of one of the K timed steps.
 
-Extra objects on the line:
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs), so that two builds can be
+compared output for output.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds these objects, each measured by
+runs of its own after the timed steps (side_measurements):
   roofline      dominant kernel of the step, timed live with HIP events on the stream it runs on
   cpu_baseline  the CPU oracle (oracle/otvae_oracle.py, a port pinned to the reference by golden vectors) timed on the
                 host cores of this box on a bounded sample of the same step (rank 0, N == 1 only)
   parity        relative error of the GPU step's losses vs that oracle on identical inputs (fp32, tolerance 1e-4)
+and beside them the per-family table, the issue bounds of the attention stages, the eager and Lightning routes and, with
+--workload sinkhorn, the OT solve alone.
 """
 import argparse
 import json
@@ -637,6 +644,117 @@ def pmc_traffic(kernel):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, trainer, latent_model, loss):
+    """What the last timed step handed its caller, one ``<name>.npy`` per array in float32 (float64 where the step keeps
+    float64): the loss vector [total, recon, prior], the latents, the flat parameters after Adam, the flat gradient Adam read,
+    the model's floating-point buffers (BatchNorm running statistics) and the latent Gaussian statistics.  An array that would
+    take the files past 64 MB in all is written as a fixed, seeded sample of its elements."""
+    import numpy as np
+    arrays = {"loss": loss, "latents": trainer.latents, "params": trainer.pflat, "grads": trainer.gflat,
+              "model_buffers": [b for b in trainer.model.buffers() if b.is_floating_point()],
+              "latent_stats": [b for b in latent_model.buffers() if b.is_floating_point()]}
+    arrays = {k: v for k, v in arrays.items() if v is not None and not (isinstance(v, list) and not v)}
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for i, (name, t) in enumerate(arrays.items()):
+        if isinstance(t, list):
+            dt = torch.float64 if any(b.dtype == torch.float64 for b in t) else torch.float32
+            t = torch.cat([b.detach().reshape(-1).to(dt) for b in t])
+        a = t.detach().cpu()
+        a = (a.double() if a.dtype == torch.float64 else a.float()).numpy()
+        keep = min(a.size, budget // (len(arrays) - i) // a.itemsize)  # an equal share of what is left
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        budget -= a.nbytes
+
+
+def side_measurements(A, args, trainer, pool, world):
+    """What ``--full`` adds to the line, each from runs of its own after the timed steps: the roofline of the kernel with the
+    largest aggregate share of the step and the per-family table, the longest launch against HBM and the issue bounds, the
+    head-width-2 attention stages, the Sinkhorn solve alone (``--workload sinkhorn``), and on one rank the eager and Lightning
+    routes, parity with the CPU oracle and the CPU baseline."""
+    line = {}
+    agg = time_largest_aggregate_kernel(A, args.workload)
+    try:
+        longest, longest_err = time_dominant_kernel(A, trainer), None
+    except Exception as e:  # noqa: BLE001  (an auxiliary measurement must not take the headline line with it)
+        longest, longest_err = None, repr(e)
+    if agg is not None:
+        gbs = agg["alg_bytes"] / (agg["ms"] * 1e-3) / 1e9
+        tfl = agg["alg_flops"] / (agg["ms"] * 1e-3) / 1e12
+        tfl_exec = agg["executed_flops"] / (agg["ms"] * 1e-3) / 1e12
+        tfl_pad = agg["padded_flops"] / (agg["ms"] * 1e-3) / 1e12
+        # The kernel with the largest aggregate share of the step.  Its launches average ~10 MB and ~0.7 GFLOP of
+        # algorithmic work: ~67 FLOP/B against a ridge at 157.3 TFLOP/s / 8 TB/s = 19.7 FLOP/B, so the fp32 MFMA roof is the
+        # one that bounds it (at that peak a launch would take ~4.5 us, at the HBM peak ~1.3 us); the HBM figures ride along.
+        t_mfma, t_hbm = agg["alg_flops"] / (FP32_MFMA_PEAK_TFLOPS * 1e12), agg["alg_bytes"] / (HBM_PEAK_GBS * 1e9)  # (live MACs)
+        hbm = {"achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 5)}
+        # achieved / frac price the LIVE multiply-adds (operands that exist; `_job_flops`); beside them the work the kernel issues
+        # (dead taps dropped, padded positions multiplied by zeros) and the padded convention of SURVEY 8(d) / rounds 1-3
+        mfma = {"achieved": round(tfl, 3), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tfl / FP32_MFMA_PEAK_TFLOPS, 5),
+                "frac_live": round(tfl / FP32_MFMA_PEAK_TFLOPS, 5), "frac_executed": round(tfl_exec / FP32_MFMA_PEAK_TFLOPS, 5),
+                "frac_padded": round(tfl_pad / FP32_MFMA_PEAK_TFLOPS, 5)}
+        main_roof, other = (("mfma", mfma), ("hbm", hbm)) if t_mfma >= t_hbm else (("hbm", hbm), ("mfma", mfma))
+        line["roofline"] = {"bound": main_roof[0], "kernel": agg["kernel"], **main_roof[1], "traffic": agg["pmc_traffic_bytes"],
+                            "avg_launch_ms": round(agg["ms"], 5), "launches_per_step": agg["launches_per_step"],
+                            "alg_bytes_per_launch": round(agg["alg_bytes"]), "alg_flops_per_launch": round(agg["alg_flops"]),
+                            "executed_flops_per_launch": round(agg["executed_flops"]),
+                            "alg_flops_padded_per_launch": round(agg["padded_flops"]),
+                            other[0]: other[1]}
+        try:
+            line["families"] = family_table(agg["trace"], trainer, world)
+        except Exception as e:  # noqa: BLE001
+            line["families"] = {"error": repr(e)}
+    # the longest single launch of the step (attention backward of the decoder's last block) against HBM and against the
+    # bound that actually holds it: vector-instruction issue (2 v_exp_f32 at 8 cycles + 5 packed FMA/MUL at 4 per 2
+    # (query, key) pairs; 1024 SIMDs at the 2.4 GHz peak clock)
+    if longest is None:
+        line["roofline_longest_launch"] = line["roofline_issue"] = {"error": longest_err}
+    else:
+        achieved = longest["alg_bytes"] / (longest["ms"] * 1e-3) / 1e9
+        tp = longest["pair_evals"] / longest["ms"] / 1e9
+        line["roofline_longest_launch"] = {"bound": "hbm", "kernel": longest["kernel"], "achieved": round(achieved, 2),
+                                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                                           "traffic": longest["pmc_traffic_bytes"], "avg_launch_ms": round(longest["ms"], 4)}
+        # `frac` = against the ALGORITHM's minimum (1 exp + 7 FMA per pair); `frac_own_isa` = against the kernel's own instruction
+        # stream (what rounds 1-3 called frac: it cannot say whether fewer instructions would do)
+        line["roofline_issue"] = {"bound": "valu_issue", "kernel": longest["kernel"], "achieved": round(tp, 3),
+                                  "peak": round(ALG_ISSUE_BOUND_TPAIRS["bwd"], 3), "unit": "T (query,key) pairs/s",
+                                  "frac": round(tp / ALG_ISSUE_BOUND_TPAIRS["bwd"], 4),
+                                  "peak_definition": "algorithmic minimum: 1 v_exp_f32 (8 issue cycles) + 5 FMA as packed pairs (2 cycles each) per pair (dq from the forward's moments)",
+                                  "peak_own_isa": round(ISSUE_BOUND_TPAIRS, 3), "frac_own_isa": round(tp / ISSUE_BOUND_TPAIRS, 4)}
+        tpf = longest["pair_evals"] / longest["ms_fwd"] / 1e9
+        line["roofline_issue_fwd"] = {"bound": "valu_issue", "kernel": "attn_stage_fwd_kernel<1,4,true> (T=1024,H=1,C=1)",
+                                      "avg_launch_ms": round(longest["ms_fwd"], 4), "achieved": round(tpf, 3),
+                                      "peak": round(ALG_ISSUE_BOUND_TPAIRS["fwd"], 3), "unit": "T (query,key) pairs/s",
+                                      "frac": round(tpf / ALG_ISSUE_BOUND_TPAIRS["fwd"], 4),
+                                      "peak_definition": "algorithmic minimum: 1 v_exp_f32 (8 issue cycles) + 3 FMA as packed pairs (2 cycles each) per pair"}
+    try:
+        line["roofline_issue_c2"] = {"bound": "valu_issue", **time_attention_c2(A)}
+    except Exception as e:  # noqa: BLE001
+        line["roofline_issue_c2"] = {"error": repr(e)}
+    if args.workload == "sinkhorn":
+        line["sinkhorn"] = time_sinkhorn(A)
+    if world == 1:
+        line["eager_ms_per_step"] = round(time_eager_route(A, args.workload, pool), 4)
+        try:
+            line["lightning_route_ms_per_step"] = round(time_lightning_route(A, args.workload, pool), 4)
+        except Exception as e:  # noqa: BLE001
+            line["lightning_route_ms_per_step"] = {"error": repr(e)}
+        try:
+            line["parity"] = parity_check(A)
+        except Exception as e:  # noqa: BLE001
+            line["parity"] = {"error": repr(e)}
+        if not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(A)
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -646,6 +764,10 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--workload", choices=["gaussian", "sinkhorn"], default="gaussian",
                     help="gaussian = BASELINE configs[1] (the metric's configuration, default); sinkhorn = configs[2]")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements (rooflines, kernel families, eager / Lightning routes, parity, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -705,14 +827,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     final_loss = [float(v) for v in out.tolist()]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, latent_model, out)
 
     if rank == 0:
         ips = world * B * args.steps / dt
-        agg = time_largest_aggregate_kernel(A, args.workload)
-        try:
-            longest, longest_err = time_dominant_kernel(A, trainer), None
-        except Exception as e:  # noqa: BLE001  (an auxiliary measurement must not take the headline line with it)
-            longest, longest_err = None, repr(e)
         line = {
             "metric": "training images/sec (whole node) + OT-loss rel-err vs CPU ref",
             "value": round(ips, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -736,74 +855,8 @@ def main():
                               "alg_tflops": round(ips / world * ALG_FLOP_PER_IMAGE_FWD_BWD / 1e12, 3),
                               "frac_of_fp32_peak": round(ips / world * ALG_FLOP_PER_IMAGE_FWD_BWD / 1e12 / FP32_VALU_PEAK_TFLOPS, 5)},
         }
-        if agg is not None:
-            gbs = agg["alg_bytes"] / (agg["ms"] * 1e-3) / 1e9
-            tfl = agg["alg_flops"] / (agg["ms"] * 1e-3) / 1e12
-            tfl_exec = agg["executed_flops"] / (agg["ms"] * 1e-3) / 1e12
-            tfl_pad = agg["padded_flops"] / (agg["ms"] * 1e-3) / 1e12
-            # The kernel with the largest aggregate share of the step.  Its launches average ~10 MB and ~0.7 GFLOP of
-            # algorithmic work: ~67 FLOP/B against a ridge at 157.3 TFLOP/s / 8 TB/s = 19.7 FLOP/B, so the fp32 MFMA roof is the
-            # one that bounds it (at that peak a launch would take ~4.5 us, at the HBM peak ~1.3 us); the HBM figures ride along.
-            t_mfma, t_hbm = agg["alg_flops"] / (FP32_MFMA_PEAK_TFLOPS * 1e12), agg["alg_bytes"] / (HBM_PEAK_GBS * 1e9)  # (live MACs)
-            hbm = {"achieved": round(gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gbs / HBM_PEAK_GBS, 5)}
-            # achieved / frac price the LIVE multiply-adds (operands that exist; `_job_flops`); beside them the work the kernel issues
-            # (dead taps dropped, padded positions multiplied by zeros) and the padded convention of SURVEY 8(d) / rounds 1-3
-            mfma = {"achieved": round(tfl, 3), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tfl / FP32_MFMA_PEAK_TFLOPS, 5),
-                    "frac_live": round(tfl / FP32_MFMA_PEAK_TFLOPS, 5), "frac_executed": round(tfl_exec / FP32_MFMA_PEAK_TFLOPS, 5),
-                    "frac_padded": round(tfl_pad / FP32_MFMA_PEAK_TFLOPS, 5)}
-            main_roof, other = (("mfma", mfma), ("hbm", hbm)) if t_mfma >= t_hbm else (("hbm", hbm), ("mfma", mfma))
-            line["roofline"] = {"bound": main_roof[0], "kernel": agg["kernel"], **main_roof[1], "traffic": agg["pmc_traffic_bytes"],
-                                "avg_launch_ms": round(agg["ms"], 5), "launches_per_step": agg["launches_per_step"],
-                                "alg_bytes_per_launch": round(agg["alg_bytes"]), "alg_flops_per_launch": round(agg["alg_flops"]),
-                                "executed_flops_per_launch": round(agg["executed_flops"]),
-                                "alg_flops_padded_per_launch": round(agg["padded_flops"]),
-                                other[0]: other[1]}
-            try:
-                line["families"] = family_table(agg["trace"], trainer, world)
-            except Exception as e:  # noqa: BLE001
-                line["families"] = {"error": repr(e)}
-        # the longest single launch of the step (attention backward of the decoder's last block) against HBM and against the
-        # bound that actually holds it: vector-instruction issue (2 v_exp_f32 at 8 cycles + 5 packed FMA/MUL at 4 per 2
-        # (query, key) pairs; 1024 SIMDs at the 2.4 GHz peak clock)
-        if longest is None:
-            line["roofline_longest_launch"] = line["roofline_issue"] = {"error": longest_err}
-        else:
-            achieved = longest["alg_bytes"] / (longest["ms"] * 1e-3) / 1e9
-            tp = longest["pair_evals"] / longest["ms"] / 1e9
-            line["roofline_longest_launch"] = {"bound": "hbm", "kernel": longest["kernel"], "achieved": round(achieved, 2),
-                                               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                                               "traffic": longest["pmc_traffic_bytes"], "avg_launch_ms": round(longest["ms"], 4)}
-            # `frac` = against the ALGORITHM's minimum (1 exp + 7 FMA per pair); `frac_own_isa` = against the kernel's own instruction
-            # stream (what rounds 1-3 called frac: it cannot say whether fewer instructions would do)
-            line["roofline_issue"] = {"bound": "valu_issue", "kernel": longest["kernel"], "achieved": round(tp, 3),
-                                      "peak": round(ALG_ISSUE_BOUND_TPAIRS["bwd"], 3), "unit": "T (query,key) pairs/s",
-                                      "frac": round(tp / ALG_ISSUE_BOUND_TPAIRS["bwd"], 4),
-                                      "peak_definition": "algorithmic minimum: 1 v_exp_f32 (8 issue cycles) + 5 FMA as packed pairs (2 cycles each) per pair (dq from the forward's moments)",
-                                      "peak_own_isa": round(ISSUE_BOUND_TPAIRS, 3), "frac_own_isa": round(tp / ISSUE_BOUND_TPAIRS, 4)}
-            tpf = longest["pair_evals"] / longest["ms_fwd"] / 1e9
-            line["roofline_issue_fwd"] = {"bound": "valu_issue", "kernel": "attn_stage_fwd_kernel<1,4,true> (T=1024,H=1,C=1)",
-                                          "avg_launch_ms": round(longest["ms_fwd"], 4), "achieved": round(tpf, 3),
-                                          "peak": round(ALG_ISSUE_BOUND_TPAIRS["fwd"], 3), "unit": "T (query,key) pairs/s",
-                                          "frac": round(tpf / ALG_ISSUE_BOUND_TPAIRS["fwd"], 4),
-                                          "peak_definition": "algorithmic minimum: 1 v_exp_f32 (8 issue cycles) + 3 FMA as packed pairs (2 cycles each) per pair"}
-        try:
-            line["roofline_issue_c2"] = {"bound": "valu_issue", **time_attention_c2(A)}
-        except Exception as e:  # noqa: BLE001
-            line["roofline_issue_c2"] = {"error": repr(e)}
-        if args.workload == "sinkhorn":
-            line["sinkhorn"] = time_sinkhorn(A)
-        if world == 1:
-            line["eager_ms_per_step"] = round(time_eager_route(A, args.workload, pool), 4)
-            try:
-                line["lightning_route_ms_per_step"] = round(time_lightning_route(A, args.workload, pool), 4)
-            except Exception as e:  # noqa: BLE001
-                line["lightning_route_ms_per_step"] = {"error": repr(e)}
-            try:
-                line["parity"] = parity_check(A)
-            except Exception as e:  # noqa: BLE001
-                line["parity"] = {"error": repr(e)}
-            if not args.no_cpu_baseline:
-                line["cpu_baseline"] = cpu_baseline(A)
+        if args.full:
+            line.update(side_measurements(A, args, trainer, pool, world))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -1340,7 +1340,7 @@ def test_bench_two_rank_call_sequence_on_one_gpu():
     port = 29700 + os.getpid() % 200
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6",
-                        "--warmup", "3"], capture_output=True, text=True, timeout=240, env=env, cwd=root)
+                        "--warmup", "3", "--full"], capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -1351,3 +1351,36 @@ def test_bench_two_rank_call_sequence_on_one_gpu():
     assert all(0 < v < 10 for v in d["final_loss"])
     for key in ("roofline", "roofline_issue"):
         assert key in d
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain ``bench.py`` run prints the headline line without the side measurements (those need ``--full``), times exactly
+    ``--steps`` steps, and ``--dump-outputs DIR`` writes the last timed step's arrays as float32 / float64 ``.npy`` files
+    (64 MB at most) that a second run with the same arguments reproduces."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=240, cwd=root)
+        assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines.append(json.loads(js[0]))
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 1024 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    for key in ("roofline", "families", "roofline_issue", "eager_ms_per_step", "parity", "cpu_baseline"):
+        assert key not in d
+    a, b = dumps
+    assert {"loss", "latents", "params", "grads", "model_buffers", "latent_stats"} <= set(a) and set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), name
+        assert np.allclose(v, b[name], rtol=1e-5, atol=1e-7), name
+    assert np.allclose(a["loss"], d["final_loss"], rtol=1e-6)

@@ -12,22 +12,22 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/final
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- python3 "$R/bench.py" > "$O/trace_bench.json" 2> "$O/trace.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- python3 "$R/bench.py" --full > "$O/trace_bench.json" 2> "$O/trace.err"
 echo "[final] trace done"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$O/pmc_fetch" -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_fetch.json" 2> "$O/pmc_fetch.err"
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$O/pmc_fetch" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_fetch.json" 2> "$O/pmc_fetch.err"
 echo "[final] pmc fetch done"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$O/pmc_write" -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_write.json" 2> "$O/pmc_write.err"
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$O/pmc_write" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_write.json" 2> "$O/pmc_write.err"
 echo "[final] pmc write done"
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$O/pmc_mfma" -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_mfma.json" 2> "$O/pmc_mfma.err"
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$O/pmc_mfma" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_mfma.json" 2> "$O/pmc_mfma.err"
 echo "[final] pmc mfma done"
-rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES --kernel-trace --output-format csv -d "$O/pmc_sq" -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_sq.json" 2> "$O/pmc_sq.err"
+rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES --kernel-trace --output-format csv -d "$O/pmc_sq" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_sq.json" 2> "$O/pmc_sq.err"
 echo "[final] pmc sq done"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_sk" -- python3 "$R/bench.py" --workload sinkhorn --no-cpu-baseline --steps 20 --warmup 5 > "$O/trace_sk.json" 2> "$O/trace_sk.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_sk" -- python3 "$R/bench.py" --full --workload sinkhorn --no-cpu-baseline --steps 20 --warmup 5 > "$O/trace_sk.json" 2> "$O/trace_sk.err"
 echo "[final] sinkhorn trace done"
 cd "$R"
-python3 bench.py > "$O/bench.json" 2> "$O/bench.err"
+python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"
 echo "[final] bench done"
-python3 bench.py --workload sinkhorn --no-cpu-baseline > "$O/bench_sinkhorn.json" 2> "$O/bench_sinkhorn.err"
+python3 bench.py --full --workload sinkhorn --no-cpu-baseline > "$O/bench_sinkhorn.json" 2> "$O/bench_sinkhorn.err"
 echo "[final] sinkhorn bench done"
 python3 tests/ot_paths_timing.py > "$O/ot_paths.txt" 2>&1
 python3 tools/eigh_bench.py > "$O/eigh_bench.txt" 2>&1
