@@ -581,6 +581,25 @@ int otvae_gauss_stats(int in_dtype, const void* samples, int nb, int B, int D, i
 int otvae_mean_cov(const double* n_obs, const double* sum_x, const double* sum_xx, int nb, int D, int diag,
                    double* mean, double* cov, void* stream);
 
+/* ---- validation metrics (csrc/metrics.hip) ---------------------------------------------------------------- */
+/* Streaming feature moments of the Frechet distance: what FrechetInceptionDistance._extract_features / update keep per side
+ * (metrics/fid.py:99-122: features.sum(0), features.T @ features, the observation count) and mean_cov (ot/matrix_utils.py:145-158)
+ * consumes.  feats [B][D] (in_dtype 0 = fp32, 1 = fp64), 1 <= B, 1 <= D <= 2048; ADDS B to n_obs[1], sum_b f_b to sum_x[D] and
+ * sum_b f_b f_b^T to sum_xx[D][D] (all fp64) in place on the fp64 matrix cores.  Only the lower triangle is computed; every element is
+ * stored to [i][j] and [j][i], so a state that starts symmetric stays bit-symmetric.  Fixed reduction order, no atomics.
+ * ws: otvae_moments_accum_ws(B, D) bytes (may be NULL when that is 0) -- at most (4 * D64^2 + 264 * D64) * 8 bytes with D64 = D
+ * rounded up to a multiple of 64, whatever B is: below 4.2 * D^2 * 8 from D = 1024 on, and 0 from D = 1985 on (wide features are
+ * not split over the batch). */
+int64_t otvae_moments_accum_ws(int B, int D); /* bytes; -1: bad argument */
+int otvae_moments_accum(int in_dtype, const void* feats, int B, int D, double* n_obs, double* sum_x, double* sum_xx, void* ws,
+                        void* stream);
+/* PeakSignalNoiseRatio's accumulation in one pass over both tensors (in_dtype as above, numel elements each): state[0] += sum (p - t)^2
+ * (differences and sum in fp64), state[1] += numel, state[2] = min(state[2], min target), state[3] = max(state[3], max target).
+ * state: otvae_sqerr_state_words() doubles -- the four above followed by scratch of the two-stage fixed-order reduction.  A fresh
+ * state is {0, 0, +inf, -inf, ...}. */
+int otvae_sqerr_state_words(void);
+int otvae_sqerr_accum(int in_dtype, const void* preds, const void* target, int64_t numel, double* state, void* stream);
+
 /* ---- symmetric eigen-decomposition based matrix functions (ot/matrix_utils.py:37-109) --------------------- */
 /* A[nb][D][D] fp64 symmetric (lower triangle is read, like eigh(UPLO='L')).  fn: 0 = none (eigvals only),
  * 1 = sqrtm, 2 = invsqrtm: out[nb][D][D] = V f(lambda) V^T; 3 = eigenvectors: out[nb][k][:] is the unit eigenvector of

@@ -8,5 +8,6 @@ from .prior import *  # noqa: F401,F403
 from .model import *  # noqa: F401,F403
 from .ot import *  # noqa: F401,F403
 from .engine import *  # noqa: F401,F403
+from . import metrics  # noqa: F401
 
 __version__ = "0.1.0"

@@ -167,6 +167,10 @@ SIGNATURES = {
     "otvae_gauss_stats_ws": (i64, [i32, i32, i32, i32]),
     "otvae_gauss_stats": (i32, [i32, vp, i32, i32, i32, i32, i32, f64, vp, vp, vp, vp, vp]),
     "otvae_mean_cov": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "otvae_moments_accum_ws": (i64, [i32, i32]),
+    "otvae_moments_accum": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "otvae_sqerr_state_words": (i32, []),
+    "otvae_sqerr_accum": (i32, [i32, vp, vp, i64, vp, vp]),
     "otvae_eigh_ws": (i64, [i32, i32]),
     "otvae_eigh_onesided_ws": (i64, [i32, i32]),
     "otvae_eigh_block_onesided_ws": (i64, [i32, i32]),

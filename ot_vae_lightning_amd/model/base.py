@@ -86,7 +86,65 @@ class VisionModule(_Base):
         self.inference = False
 
     on_validation_epoch_start = on_test_epoch_start = on_predict_epoch_start = _ema_swap_in
-    on_validation_epoch_end = on_test_epoch_end = on_predict_epoch_end = _ema_swap_out
+    on_predict_epoch_end = _ema_swap_out
+
+    def on_validation_epoch_end(self, *args):
+        """compute, log and reset the validation metrics while the averaged weights are still in (the reference does this in
+        ``validation_epoch_end``, which Lightning runs before this hook), then swap the training weights back"""
+        res = self._compute_and_log_metric("val")
+        self._ema_swap_out()
+        return res
+
+    def on_test_epoch_end(self, *args):
+        res = self._compute_and_log_metric("test")
+        self._ema_swap_out()
+        return res
+
+    # ---- evaluation metrics: the reference's hooks (model/base.py:131-135,144-148,174-186,197-220)
+    def on_validation_start(self) -> None:
+        return self._prepare_metrics("val")
+
+    def on_test_start(self) -> None:
+        return self._prepare_metrics("test")
+
+    def validation_step(self, batch, batch_idx, dataloader_idx=0):
+        return self._update_metrics(batch, batch_idx, "val")
+
+    def test_step(self, batch, batch_idx, dataloader_idx=0):
+        return self._update_metrics(batch, batch_idx, "test")
+
+    @torch.no_grad()
+    def _prepare_metrics(self, mode):
+        """a metric that has something to do once before the run (e.g. statistics of the real data) declares ``prepare_metric(model)``"""
+        collection = getattr(self, f"{mode}_metrics")
+        if collection is None:
+            return
+        for _, metric in collection.items():
+            if hasattr(metric, "prepare_metric"):
+                metric.prepare_metric(self)
+
+    @torch.no_grad()
+    def _update_metrics(self, batch, batch_idx, mode):
+        collection = getattr(self, f"{mode}_metrics")
+        if collection is None:
+            return
+        pbatch = self.batch_preprocess(batch)
+        kwargs = pbatch["kwargs"] if "kwargs" in pbatch else {}
+        pbatch["preds"] = self(pbatch["samples"], **kwargs)
+        if hasattr(self, "sample"):
+            pbatch["generated"] = self.sample(pbatch["samples"].size(0), **kwargs)
+        collection.update(**pbatch)   # each metric takes the keywords its own `update` names
+        return pbatch
+
+    def _compute_and_log_metric(self, mode):
+        collection = getattr(self, f"{mode}_metrics")
+        if collection is None:
+            return
+        collection.sync()             # all-reduce of every state; a no-op without an initialised process group
+        res = collection.compute()
+        collection.reset()
+        self.log_dict(res, sync_dist=True, prog_bar=True, logger=True)
+        return res
 
     def training_step(self, batch, batch_idx, optimizer_idx=0):
         loss_fn = self.loss[optimizer_idx] if hasattr(self.loss, "__getitem__") else self.loss

@@ -12,6 +12,9 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
     otvae::gaussian_w2_prior        _stats -> mean_cov -> w2_gaussian            gaussian_model.py:144-157, matrix_utils.py:145-158,
                                                                                  w2_utils.py:40-80
 
+    otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
+    otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
+
 The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the two OT priors).
 ``ConvBlock`` runs its two branches and the training engine's in-place gradient slots through the packed variant of the
 same kernels (``functional.conv_layers``); ``otvae::conv_bn_act`` is the single-layer functional form.
@@ -448,3 +451,46 @@ def _w2_backward(ctx, g, _gmu, _gq, _gvt):
 
 
 torch.library.register_autograd("otvae::gaussian_w2_prior", _w2_backward, setup_context=_w2_setup)
+
+
+# ------------------------------------------------------------------------------------------------ validation metrics
+# In-place accumulators like ``bn_batch_stats``' running buffers: the states are mutated, nothing is returned, nothing is differentiable.
+def _moments_accum(feats: Tensor, n_obs: Tensor, sum_x: Tensor, sum_xx: Tensor) -> None:
+    lib = _lib.load()
+    _lib.require_cuda(feats, "features")
+    if feats.dim() != 2 or feats.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"moments_accum takes [B, D] float32 / float64 features, got {tuple(feats.shape)} {feats.dtype}")
+    b, d = feats.shape
+    if b == 0:
+        return
+    for name, t, shape in (("n_obs", n_obs, (1,)), ("sum_x", sum_x, (d,)), ("sum_xx", sum_xx, (d, d))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"moments_accum: {name} must be a contiguous float64 tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+    nbytes = lib.otvae_moments_accum_ws(b, d)
+    if nbytes < 0:
+        raise ValueError(f"moments_accum: feature width {d} is beyond the kernel's 2048")
+    feats = feats.contiguous()
+    ws = torch.empty(nbytes, device=feats.device, dtype=torch.uint8) if nbytes else None
+    check(lib.otvae_moments_accum(0 if feats.dtype == torch.float32 else 1, ptr(feats), b, d, ptr(n_obs), ptr(sum_x), ptr(sum_xx), ptr(ws),
+                                  stream()), "otvae_moments_accum")
+
+
+def _sqerr_accum(preds: Tensor, target: Tensor, state: Tensor) -> None:
+    lib = _lib.load()
+    _lib.require_cuda(preds, "preds")
+    if preds.shape != target.shape:
+        raise ValueError(f"sqerr_accum: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
+    if preds.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"sqerr_accum takes float32 / float64 tensors, got {preds.dtype}")
+    if state.dtype != torch.float64 or state.numel() != lib.otvae_sqerr_state_words() or not state.is_contiguous():
+        raise ValueError(f"sqerr_accum: state must be {lib.otvae_sqerr_state_words()} contiguous float64 words")
+    if preds.numel() == 0:
+        return
+    preds, target = preds.contiguous(), target.to(preds.dtype).contiguous()
+    check(lib.otvae_sqerr_accum(0 if preds.dtype == torch.float32 else 1, ptr(preds), ptr(target), preds.numel(), ptr(state), stream()),
+          "otvae_sqerr_accum")
+
+
+_define("moments_accum", "(Tensor feats, Tensor(a!) n_obs, Tensor(b!) sum_x, Tensor(c!) sum_xx) -> ()", _moments_accum,
+        lambda feats, n_obs, sum_x, sum_xx: None)
+_define("sqerr_accum", "(Tensor preds, Tensor target, Tensor(a!) state) -> ()", _sqerr_accum, lambda preds, target, state: None)
