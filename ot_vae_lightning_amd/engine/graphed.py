@@ -16,18 +16,18 @@ statistics, RNG counters) advances inside the replayed graphs exactly as in the 
 """
 from __future__ import annotations
 
-import os
+import copy
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from .. import _lib
-
-from .lifetime import GraphSet, capture_guard
+from .. import functional as HF
+from .lifetime import GraphSet, capture_guard, capture_kwargs, warm_up
 from .segments import SEGMENT_CALLS, SegmentedStep
-from .trainer import HipTrainer, _dense_view
+from .state import restore, snapshot, step_state
+from .trainer import HipTrainer, _dense_view, slots_resumed
 
 __all__ = ["GraphedNelbo"]
 
@@ -93,7 +93,6 @@ class GraphedNelbo:
     def __deepcopy__(self, memo):
         """``copy.deepcopy(model)`` copies ``model.loss`` with it: the copy must point at the COPIED model (a weak reference is atomic
         for deepcopy: it would keep pointing at the original) and starts without captured graphs (it captures on its first call)."""
-        import copy
         m = self._model_ref()
         twin = memo.get(id(m)) if m is not None else None
         if twin is None:
@@ -128,7 +127,6 @@ class GraphedNelbo:
                 tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in kw.items() if isinstance(v, Tensor))))
 
     def _capture(self, batch) -> _Capture:
-        from .. import functional as HF
         model = self.model
         samples, kwargs = batch["samples"], batch["kwargs"]
         old = self._cap
@@ -149,7 +147,7 @@ class GraphedNelbo:
         cap = _Capture()
         cap.key, cap.engine = self._key(batch), engine
         cap.graphs = GraphSet(engine.device)
-        weakref.finalize(cap, GraphSet.release, cap.graphs).atexit = False   # (see HipTrainer: not at interpreter exit)
+        cap.graphs.attach(cap)
         cap.params = engine.params
         cap.seed = torch.tensor([1.0, 0.0, 0.0], device=engine.device)
         engine._seed = cap.seed
@@ -171,11 +169,8 @@ class GraphedNelbo:
                 p.grad = None
             # the backward pass's statistic slots lie behind the forward pass's; zeroed again here: this graph may be replayed more than
             # once per forward replay (retain_graph)
-            HF.SlotArena.resume(engine.device, rezero=True)
-            try:
+            with slots_resumed(engine.device, rezero=True):
                 engine._backward(loss)
-            finally:
-                HF.SlotArena.end_step(engine.device)
             HF._PendingReduce.flush(engine.device)
             engine._collect_loose_grads()
             for p in engine.params:    # the captured pass's own p.grad objects must not outlive the capture
@@ -186,28 +181,19 @@ class GraphedNelbo:
             model._last_nelbo = None
 
         # everything a step mutates besides what the optimizer owns: restored after warm-up + capture
-        flat_ids = {id(p) for p in engine.params}
-        state = [t for t in model.buffers()] + [p.data for p in model.parameters() if id(p) not in flat_ids]
-        state += [m.__dict__["_dropout_key"] for m in model.modules() if isinstance(m.__dict__.get("_dropout_key"), Tensor)]
-        snap = [t.clone() for t in state]
-        s = _lib.fresh_stream(engine.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(self.warmup):
-                backward(forward()[0])
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        mode = dict(capture_error_mode=os.environ.get("OTVAE_CAPTURE_ERROR_MODE", "thread_local"))
-        cstream = _lib.fresh_stream(engine.device)   # ONE capture stream for the forward and the backward graphs (segments.py)
+        state = step_state(model, engine.params, engine.eps.shape, engine.device)
+        snap = snapshot(state)
+        warm_up(engine.device, lambda: backward(forward()[0]), self.warmup)
+        mode = capture_kwargs(engine.device)   # ONE capture stream for the forward and the backward graphs (segments.py)
         with capture_guard():
-            with torch.cuda.graph(cap.graphs.new("f"), stream=cstream, **mode):
+            with torch.cuda.graph(cap.graphs.new("f"), **mode):
                 loss, logs, art = forward()
                 cap.out3 = model._last_nelbo
             pool = cap.graphs.get("f").pool()
             if SEGMENT_CALLS > 0 and HF.WGRAD_SIDE_STREAM == 1:
                 # the backward pass as a chain of linear graphs + side graphs (engine/segments.py): ~0.1 ms of host time per replay
                 # instead of ~0.8 ms for one graph with a fork per layer, which matters on this host-bound route
-                seg = SegmentedStep(engine.device, HF._PendingReduce.side_stream(engine.device), pool=pool, stream=cstream)
+                seg = SegmentedStep(engine.device, HF._PendingReduce.side_stream(engine.device), pool=pool, stream=mode["stream"])
                 cap.graphs.put("b", seg)
                 HF._PendingReduce.begin_segments(engine.device, seg)
                 try:
@@ -217,7 +203,7 @@ class GraphedNelbo:
                     HF._PendingReduce.end_segments(engine.device)
                 del seg
             else:
-                with torch.cuda.graph(cap.graphs.new("b"), pool=pool, stream=cstream, **mode):
+                with torch.cuda.graph(cap.graphs.new("b"), pool=pool, **mode):
                     backward(loss)
         cap.out3 = cap.out3.detach()
         # tensors only (preds, latents, preds_mean ...): a prior's lazily built distribution objects could hold the captured pass's
@@ -226,9 +212,7 @@ class GraphedNelbo:
         del loss, logs, art
         model._last_nelbo = None
         model._last_cut = None
-        with torch.no_grad():
-            for t, v in zip(state, snap):
-                t.copy_(v)
+        restore(state, snap)
         torch.cuda.synchronize()
         return cap
 

@@ -21,19 +21,24 @@ Rules enforced here:
 * every capture of this package runs inside ``capture_guard()``: parked graphs are destroyed before the capture begins and the
   cyclic collector is switched off until it ends, so that no destructor of a foreign object graph (a user's own dropped
   ``CUDAGraph`` in a cycle) can run inside it either;
-* owners attach ``weakref.finalize(owner, GraphSet.release, graphset)``: an owner that is dropped without ``close()`` releases
-  its graphs through the same ordered path the moment it dies (the finalizers are NOT run at interpreter exit: no capture can be
-  open there, and what is still alive then goes down with the process as it always has).
+* owners call ``GraphSet.attach(owner)``: an owner that is dropped without ``close()`` releases its graphs through the same
+  ordered path the moment it dies (the finalizers are NOT run at interpreter exit: no capture can be open there, and what is
+  still alive then goes down with the process as it always has);
+* every capture is prepared by ``warm_up`` and takes its stream and error mode from ``capture_kwargs``.
 """
 from __future__ import annotations
 
 import gc
+import os
 import threading
-from typing import Dict, List
+import weakref
+from typing import Callable, Dict, List
 
 import torch
 
-__all__ = ["GraphSet", "capture_guard", "capture_open", "drain"]
+from .._lib import fresh_stream
+
+__all__ = ["GraphSet", "capture_guard", "capture_open", "drain", "warm_up", "capture_kwargs"]
 
 _lock = threading.RLock()
 _parked: List[tuple] = []        # (device, [graph objects]) waiting for a point where destroying them is legal
@@ -98,6 +103,12 @@ class GraphSet:
     def __bool__(self) -> bool:
         return bool(self._graphs)
 
+    def attach(self, owner) -> weakref.finalize:
+        """``owner`` dying releases these graphs (not at interpreter exit: see the module docstring).  Returns the finalizer."""
+        fin = weakref.finalize(owner, GraphSet.release, self)
+        fin.atexit = False
+        return fin
+
     def release(self) -> None:
         """Idempotent.  Outside a capture: synchronise the device, destroy the graphs in reverse capture order.  Inside one: park
         them for ``drain()``."""
@@ -112,6 +123,25 @@ class GraphSet:
             return
         drain()
         _destroy(self.device, graphs)
+
+
+def warm_up(device, step: Callable[[], object], n: int) -> None:
+    """``n`` eager runs of ``step`` on a fresh stream, joined with the current one; the device is idle on return."""
+    s = fresh_stream(device)
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(n):
+            step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+
+
+def capture_kwargs(device) -> dict:
+    """Keyword arguments of every ``torch.cuda.graph(...)`` of this package: a fresh capture stream (``_lib.fresh_stream``) and
+    the error mode.  "thread_local": only this thread's calls are policed while the stream captures.  Under torch's default
+    ("global") an event query from another thread -- the RCCL watchdog polling the collectives of earlier steps -- is an illegal
+    call that kills the capture, and the process with it, whenever the poll happens to land inside it."""
+    return dict(stream=fresh_stream(device), capture_error_mode=os.environ.get("OTVAE_CAPTURE_ERROR_MODE", "thread_local"))
 
 
 class capture_guard:

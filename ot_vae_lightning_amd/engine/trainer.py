@@ -11,7 +11,7 @@ Design (DESIGN.md section "engine"):
     section 2.2), then ONE all-reduce(SUM) of the flat gradient buffer (6.6 MiB for the MNIST config) on a side stream,
     and Adam consumes ``grad / world_size``;
   * the whole step is captured once (``torch.cuda.CUDAGraph`` -> hipGraph) and replayed: no Python, no allocator and no
-    launch-latency gaps between the ~400 kernels of a step.  With more than one rank the graph is split around the
+    launch-latency gaps between the ~200 kernels of a step.  With more than one rank the graph is split around the
     collective (graph A: forward+backward, eager RCCL all-reduce, graph B: Adam).
 """
 from __future__ import annotations
@@ -19,19 +19,24 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
+from contextlib import contextmanager
 from typing import Dict, List, Optional
 
 import torch
-import torch.distributed as dist
 from torch import Tensor
 
 from .. import _lib
 from .._lib import check, ptr, stream
 from .. import functional as HF
+# (neither import is circular: the model package reaches the engine only from inside methods, and the package imports it first)
+from ..model.vae import VAE
 from ..networks.cnn import ConvLayer
+from ..utils import hasarg
 from .dp import FlatGradReducer
-from .lifetime import GraphSet, capture_guard
+from .ema import ParamEMA
+from .lifetime import GraphSet, capture_guard, capture_kwargs, warm_up
 from .segments import SEGMENT_CALLS, SegmentedStep
+from .state import restore, snapshot, step_state
 
 DP_OVERLAP_MIN_BYTES = int(os.environ.get("OTVAE_DP_OVERLAP_MIN_BYTES", str(32 << 20)))
 
@@ -58,6 +63,16 @@ def _dense_view(flat: Tensor, off: int, like: Tensor) -> Tensor:
     inv = [order.index(d) for d in range(like.dim())]
     v = flat[off: off + like.numel()].view(phys_shape)
     return v.permute(inv) if like.dim() > 0 else v.view(())
+
+
+@contextmanager
+def slots_resumed(device, rezero: bool = False):
+    """The step's BatchNorm statistic slots are handed out again inside, behind the ones already taken (functional.SlotArena)."""
+    HF.SlotArena.resume(device, rezero=rezero)
+    try:
+        yield
+    finally:
+        HF.SlotArena.end_step(device)
 
 
 def flatten_parameters(params: List[torch.nn.Parameter], align: int = 4):
@@ -111,7 +126,6 @@ class HipTrainer:
         # kernel itself (otvae_adam_step_ema); the model's epoch hooks swap it in and out around evaluation (engine/ema.py)
         self.ema = None
         if getattr(model, "ema_decay", None) is not None and not weak_model:
-            from .ema import ParamEMA
             self.ema = ParamEMA(self.params, model.ema_decay, flat=self.pflat, in_optimizer=True, step_tensor=self.step_count)
             model._ema = self.ema
         # global-norm clipping of the (rank-averaged) gradient, the reference's DDP overlay (configs/ddp.yaml:4); the two
@@ -175,6 +189,8 @@ class HipTrainer:
         # dp_overlap=True / False decide it outright.  (Which side of the threshold an 8-GPU node really is on is unmeasured here.)
         if dp_overlap is None:
             dp_overlap = default_dp_overlap(self.world, self.gflat.numel() * self.gflat.element_size(), os.environ.get("OTVAE_DP_OVERLAP"))
+        self._enc_params: List[torch.nn.Parameter] = []    # upstream of the cut
+        self._post_params: List[torch.nn.Parameter] = []   # decoder, prior: downstream of it
         self._dec_range = self._decoder_range() if dp_overlap else None
         self.dp_overlap = self._dec_range is not None
         # static I/O
@@ -204,46 +220,27 @@ class HipTrainer:
         # "opt" (Adam behind the all-reduce), or "segments" (a SegmentedStep).  The GraphSet is their ONLY strong owner; an engine
         # dropped without close() releases them through the same ordered path (engine/lifetime.py)
         self._gs = GraphSet(dev)
-        self._finalizer = weakref.finalize(self, GraphSet.release, self._gs)
-        # not at interpreter exit: no capture can be open there, and what is still alive then goes down with the process as it
-        # always has (the ordered path is for owners that die while the program runs)
-        self._finalizer.atexit = False
+        self._gs.attach(self)
         self._captured = False
         self.n_steps = 0
+        # what a step leaves for the next call (close() lets go of all of it)
+        self._out_static: Optional[Tensor] = None   # the captured step's [total, recon, prior]
+        self._logs: Optional[Dict[str, Tensor]] = None
+        self._cut: Optional[Tensor] = None          # the encoder's output between the two phases of a cut backward pass
+        self._watch: Optional[Tensor] = None        # the loss vector the optimizer kernel's guard reads
+        self._loose_params: set = set()             # ids of parameters whose gradient reaches them through plain autograd
+        self._wants_eps = False
         if self.step_guard is not None:
             self._rebase_step_state()
 
-    def _step_state_tensors(self) -> List[Tensor]:
-        """Every tensor OBJECT (buffer, parameter outside the flat buffer, RNG key ...) whose storage a training step writes besides
-        parameters / moments / gradients: all buffers of the model (BatchNorm running statistics and counters, the EMA embeddings of
-        a ConditionalGaussianPrior, GaussianW2Prior's warm-start flag), parameters the optimizer does not own (frozen ones an EMA
-        rewrites), the dropout key counters, the running statistics of the latent operator, and what modules declare through
-        ``_otvae_step_state(latent_shape, device)`` (state that is not a registered buffer: GaussianW2Prior's warm-start basis)."""
-        model = self.model
-        flat_ids = {id(p) for p in self.params}
-        ts: List[Tensor] = [b for b in model.buffers()]
-        ts += [p for p in model.parameters() if id(p) not in flat_ids]
-        for mod in model.modules():
-            key = mod.__dict__.get("_dropout_key")
-            if isinstance(key, Tensor):
-                ts.append(key)
-            decl = getattr(mod, "_otvae_step_state", None)
-            if decl is not None:
-                ts += list(decl(tuple(self.eps.shape), self.device))
-        if self.latent_stats is not None:
-            ts += [b for b in self.latent_stats.buffers()] + [p for p in self.latent_stats.parameters()]
-        seen, out = set(), []
-        for t in ts:
-            if t is None or id(t) in seen or t.numel() == 0 or t.device != self.device or not t.is_contiguous():
-                continue
-            seen.add(id(t))
-            out.append(t)
-        return out
+    def _step_state(self) -> List[Tensor]:
+        return step_state(self.model, self.params, self.eps.shape, self.device, self.latent_stats)
 
     def _rebase_step_state(self) -> None:
-        """Moves the storage of every tensor of ``_step_state_tensors`` into one flat byte range (16-byte aligned slots, any dtype:
-        the guard kernels copy 4-byte words bit for bit), ``rflat``; ``rbackup`` holds the copy a guarded step takes at its start."""
-        ts = self._step_state_tensors()
+        """Moves the storage of every tensor of ``_step_state`` (those on this device that are contiguous) into one flat byte range
+        (16-byte aligned slots, any dtype: the guard kernels copy 4-byte words bit for bit), ``rflat``; ``rbackup`` holds the copy a
+        guarded step takes at its start."""
+        ts = [t for t in self._step_state() if t.device == self.device and t.is_contiguous()]
         if not ts:
             return
         offs, total = [], 0
@@ -291,61 +288,78 @@ class HipTrainer:
                                               ptr(self.rbackup) if guarded else None, self.rflat.numel() if guarded else 0,
                                               ptr(z), z.numel() if z is not None else 0, stream()), "otvae_step_begin_slots")
 
-    def _forward_backward(self):
-        self._step_begin()
-        for p in self.params:
-            p.grad = None
-        from ..functional import PriorLane, _PendingReduce
-        PriorLane.enabled = True  # the prior's OT work may run beside the decoder: this method joins it (functional.PriorLane)
+    @contextmanager
+    def _step_scope(self):
+        """From ``_step_begin`` to the end of the backward pass: the statistic slots are open and the prior's OT work may run beside
+        the decoder (functional.PriorLane); the exit closes the slots and joins the lane."""
         # (Round 3 tried to put the step's small off-chain launches -- the refresh of the transposed weights, the loss vector, the
         # latent statistics -- on the same lane: 2.80 -> 2.86 ms at batch 1024, the extra graph branches cost more than the ~40 us
         # of launches they take off the chain; removed.)
+        HF.PriorLane.enabled = True
         try:
-            self._refresh_wd()
-            from ..functional import _PendingReduce as _PR
-            # what depends on the forward pass only and is read by nothing before the optimizer -- the loss value (ops._nelbo_fwd_launch)
-            # and the latent statistics -- goes to the side stream with the first weight-gradient fork of the backward pass (joined with
-            # it in flush); only in a captured single-graph step, where that fork exists
-            # ... and only for the package's own `VAE.nelbo`: between `nelbo()` returning and the join in `flush` the loss vector is not
-            # yet written on the launch stream, so a subclass whose nelbo READS the loss it just computed (combining terms, stacking
-            # logs) would capture garbage -- for such a model the value is launched in line
-            from ..model.vae import VAE as _VAE
-            own_nelbo = getattr(type(self.model), "nelbo", None) is _VAE.nelbo
-            on_side = (STATS_ON_SIDE and own_nelbo and self._segments is None and HF.WGRAD_SIDE_STREAM == 1 and
-                       torch.cuda.is_current_stream_capturing())
-            _PR._defer[self.device] = on_side
-            try:
-                loss, logs, art = self.model.nelbo(self._batch(), 0)
-            finally:
-                _PR._defer[self.device] = False
-            self.latents = art["latents"].detach()
-            if on_side and self.latent_stats is not None:
-                lat_, stats_ = self.latents.flatten(1), self.latent_stats
-                _PR._defer[self.device] = True
-                _PR.defer_to_side(self.device, lambda: stats_.update(target_samples=lat_), lat_)
-                _PR._defer[self.device] = False
-            self._backward(loss)
-        except BaseException:
-            # a pass that raised (in the forward pass as well: the deferred loss / statistics launches are queued there) must leave
-            # nothing behind for the next step's first fork to run against this step's tensors
-            _PendingReduce.reset(self.device)
-            raise
+            yield
         finally:
             HF.SlotArena.end_step(self.device)
-            PriorLane.enabled = False
-            PriorLane.join(self.device)  # (already joined by the prior's backward when it took part in the pass)
+            HF.PriorLane.enabled = False
+            HF.PriorLane.join(self.device)  # (already joined by the prior's backward when it took part in the pass)
+
+    def _forward_backward(self, cut: bool = False):
+        """Forward + backward.  ``cut`` (data-parallel overlap): the backward pass stops at the encoder's output h -- gradients of
+        everything downstream of it (loss, decoder, prior) and dL/dh; ``_phase2`` runs the encoder's backward and the latent
+        statistics.  Same kernels in the same order either way, up to the cut."""
+        dev, pending = self.device, HF._PendingReduce
+        self._step_begin()
+        for p in self.params:
+            p.grad = None
+        with self._step_scope():
+            try:
+                self._refresh_wd()
+                # what depends on the forward pass only and is read by nothing before the optimizer -- the loss value
+                # (ops._nelbo_fwd_launch) and the latent statistics -- goes to the side stream with the first weight-gradient fork of the
+                # backward pass (joined with it in flush); only in a captured single-graph step, where that fork exists
+                # ... and only for the package's own `VAE.nelbo`: between `nelbo()` returning and the join in `flush` the loss vector is
+                # not yet written on the launch stream, so a subclass whose nelbo READS the loss it just computed (combining terms,
+                # stacking logs) would capture garbage -- for such a model the value is launched in line (ADVICE r3)
+                own_nelbo = getattr(type(self.model), "nelbo", None) is VAE.nelbo
+                on_side = (not cut and STATS_ON_SIDE and own_nelbo and self._segments is None and HF.WGRAD_SIDE_STREAM == 1 and
+                           torch.cuda.is_current_stream_capturing())
+                pending._defer[dev] = on_side
+                try:
+                    loss, logs, art = self.model.nelbo(self._batch(), 0)
+                finally:
+                    pending._defer[dev] = False
+                self.latents = art["latents"].detach()
+                if on_side and self.latent_stats is not None:
+                    lat_, stats_ = self.latents.flatten(1), self.latent_stats
+                    pending._defer[dev] = True
+                    pending.defer_to_side(dev, lambda: stats_.update(target_samples=lat_), lat_)
+                    pending._defer[dev] = False
+                h = getattr(self.model, "_last_cut", None) if cut else None
+                if h is None:  # no cut, or nothing upstream of it needs a gradient: one-phase backward
+                    self._backward(loss)
+                else:
+                    # retain_graph: without it the engine also releases the saved tensors of the node that produced h
+                    self._backward(loss, inputs=self._post_params + [h], retain_graph=True)
+            except BaseException:
+                # a pass that raised (in the forward pass as well: the deferred loss / statistics launches are queued there) must
+                # leave nothing behind for the next step's first fork to run against this step's tensors
+                pending.reset(dev)
+                raise
+        self._cut = h
         # the model's handle on the encoder output would keep this step's autograd graph -- and with it the parameters'
         # AccumulateGrad nodes, bound to the stream they were created on -- alive into the next step (and from the
         # warm-up stream into the capture: "AccumulateGrad node's stream does not match ...")
         if hasattr(self.model, "_last_cut"):
             self.model._last_cut = None
-        _PendingReduce.flush(self.device)  # normally already done by the autograd-engine callback at the end of backward
-        self._collect_loose_grads()
+        # normally already done by the autograd-engine callback at the end of backward; with a cut: the decoder's weight gradients
+        # are complete before their all-reduce starts
+        pending.flush(dev)
+        # with a cut only the downstream parameters have their gradient now; the encoder's slots are filled by phase 2
+        self._collect_loose_grads(self._post_params if h is not None else None)
         self._logs = {k: v.detach() for k, v in logs.items()}  # no reference into the autograd graph survives the step
-        _PendingReduce.run_deferred_inline(self.device)  # (a pass without forks: nothing took the deferred work)
-        if self.latent_stats is not None and not on_side:
-            lat = self.latents.flatten(1)  # [B, D] with transport_dims = (1, 2, 3)
-            self.latent_stats.update(target_samples=lat)
+        pending.run_deferred_inline(dev)  # (a pass without forks: nothing took the deferred work)
+        if self.latent_stats is not None and not on_side and not cut:
+            self.latent_stats.update(target_samples=self.latents.flatten(1))  # [B, D] with transport_dims = (1, 2, 3)
         return self._logs
 
     def _batch(self):
@@ -357,7 +371,7 @@ class HipTrainer:
         convolution / BatchNorm kernels write their slots directly (then p.grad IS the slot): nothing to do for them.
         ``params``: the parameters whose backward has just run (two-phase backward: a slot of the other phase may already
         be under its all-reduce and must not be written)."""
-        loose = self.__dict__.setdefault("_loose_params", set())
+        loose = self._loose_params
         pairs = []
         for p in (self.params if params is None else params):
             g = p.grad
@@ -390,8 +404,7 @@ class HipTrainer:
                 torch.autograd.backward(out3, grad_tensors=[self._seed], **kw)
         except BaseException:
             # the deferred weight-gradient jobs / reductions of the interrupted pass must not leak into the next one
-            from ..functional import _PendingReduce
-            _PendingReduce.reset(self.device)
+            HF._PendingReduce.reset(self.device)
             raise
         finally:
             if out3 is not None:
@@ -410,58 +423,23 @@ class HipTrainer:
         hi = self.offsets[idx[-1] + 1] if idx[-1] + 1 < len(self.params) else self.gflat.numel()
         enc_ids = {id(p) for p in self.model.encoder.parameters()}
         self._enc_params = [p for p in self.params if id(p) in enc_ids]
-        self._post_params = [p for p in self.params if id(p) not in enc_ids]  # decoder, prior: downstream of the cut
+        self._post_params = [p for p in self.params if id(p) not in enc_ids]
         if not self._enc_params:
             return None
         return lo, hi
 
-    def _phase1(self):
-        """forward + backward of everything downstream of the encoder's output h (loss, decoder, prior): gradients of
-        their parameters and dL/dh.  Same kernels in the same order as ``_forward_backward`` up to the cut."""
-        self._step_begin()
-        self._refresh_wd()
-        for p in self.params:
-            p.grad = None
-        from ..functional import PriorLane
-        PriorLane.enabled = True
-        try:
-            loss, logs, art = self.model.nelbo(self._batch(), 0)
-            h = getattr(self.model, "_last_cut", None)
-            if h is None:  # nothing upstream of the cut needs a gradient: one-phase backward
-                self._backward(loss)
-            else:
-                # retain_graph: without it the engine also releases the saved tensors of the node that produced h
-                self._backward(loss, inputs=self._post_params + [h], retain_graph=True)
-        finally:
-            HF.SlotArena.end_step(self.device)
-            PriorLane.enabled = False
-            PriorLane.join(self.device)
-        self._cut = h
-        from ..functional import _PendingReduce
-        _PendingReduce.flush(self.device)  # the decoder's weight gradients are complete before their all-reduce starts
-        # with a cut only the downstream parameters have their gradient now; the encoder's slots are filled by phase 2
-        self._collect_loose_grads(self._post_params if h is not None else None)
-        self._logs = {k: v.detach() for k, v in logs.items()}
-        self.latents = art["latents"].detach()
-        return self._logs
-
     def _phase2(self):
-        """the encoder's backward, from dL/dh that phase 1 left at the cut"""
+        """the encoder's backward, from dL/dh that ``_forward_backward(cut=True)`` left at the cut"""
         h = self._cut
         if h is not None:
-            HF.SlotArena.resume(self.device)   # (the encoder's backward adds into slots behind the ones phase 1 took)
-            try:
+            with slots_resumed(self.device):   # (the encoder's backward adds into slots behind the ones phase 1 took)
                 torch.autograd.backward(h, h.grad, inputs=self._enc_params)
-            finally:
-                HF.SlotArena.end_step(self.device)
             h.grad = None
-            from ..functional import _PendingReduce
-            _PendingReduce.flush(self.device)
+            HF._PendingReduce.flush(self.device)
             # ONLY the encoder's: the decoder's range is under its all-reduce on the side stream right now, and its
             # p.grad (still set from phase 1) holds the rank-local value
             self._collect_loose_grads(self._enc_params)
         self._cut = None
-        self.model._last_cut = None
         if self.latent_stats is not None:
             self.latent_stats.update(target_samples=self.latents.flatten(1))
 
@@ -472,55 +450,38 @@ class HipTrainer:
         self.reducer.join()
 
     def _adam(self):
-        lib = self.lib
+        """One optimizer launch through the library's superset entry: NULL / 0 for whatever of {device-side gradient scale, step
+        guard, running-state range, parameter EMA} this engine does not use."""
+        lib, ema = self.lib, self.ema
         norm = self.gradient_clip_val is not None or self.step_guard == "full"
         if norm:  # max_norm 0: the norm is only reported (out[0] = grad_scale)
             check(lib.otvae_grad_clip_coef(ptr(self.gflat), self.gflat.numel(), self.reducer.grad_scale, self.gradient_clip_val or 0.0,
                                            ptr(self._clip_ws), ptr(self.clip_out), stream()), "otvae_grad_clip_coef")
-        if self.ema is not None:
-            guarded = self.step_guard is not None
-            watch = getattr(self.model, "_last_out3", None) if guarded else None
-            self._watch = watch
-            check(lib.otvae_adam_step_ema(ptr(self.pflat), ptr(self.gflat), ptr(self.m), ptr(self.v), self.pflat.numel(),
-                                          ptr(self.hyper), ptr(self.step_count), self.reducer.grad_scale,
-                                          ptr(self.clip_out) if norm else None, ptr(watch), ptr(self.guard) if guarded else None,
-                                          ptr(self.rflat) if guarded else None, ptr(self.rbackup) if guarded else None,
-                                          0 if (self.rflat is None or not guarded) else self.rflat.numel(),
-                                          ptr(self.ema.shadow), self.ema.decay, stream()), "otvae_adam_step_ema")
-        elif self.step_guard is not None:
-            watch = getattr(self.model, "_last_out3", None)  # [total, recon, prior] of this step (static inside a captured step)
-            self._watch = watch
-            check(lib.otvae_adam_step_guarded(ptr(self.pflat), ptr(self.gflat), ptr(self.m), ptr(self.v), self.pflat.numel(),
-                                              ptr(self.hyper), ptr(self.step_count), self.reducer.grad_scale,
-                                              ptr(self.clip_out) if norm else None, ptr(watch), ptr(self.guard),
-                                              ptr(self.rflat), ptr(self.rbackup), 0 if self.rflat is None else self.rflat.numel(),
-                                              stream()), "otvae_adam_step_guarded")
-        elif norm:
-            check(lib.otvae_adam_step_dev(ptr(self.pflat), ptr(self.gflat), ptr(self.m), ptr(self.v), self.pflat.numel(),
-                                          ptr(self.hyper), ptr(self.step_count), ptr(self.clip_out), stream()),
-                  "otvae_adam_step_dev")
-        else:
-            check(lib.otvae_adam_step(ptr(self.pflat), ptr(self.gflat), ptr(self.m), ptr(self.v), self.pflat.numel(),
-                                      ptr(self.hyper), ptr(self.step_count), self.reducer.grad_scale, stream()),
-                  "otvae_adam_step")
+        guarded = self.step_guard is not None
+        state = self.rflat if guarded else None  # (None as well when the model has no running state)
+        # [total, recon, prior] of this step (static inside a captured step)
+        self._watch = watch = getattr(self.model, "_last_out3", None) if guarded else None
+        check(lib.otvae_adam_step_ema(ptr(self.pflat), ptr(self.gflat), ptr(self.m), ptr(self.v), self.pflat.numel(),
+                                      ptr(self.hyper), ptr(self.step_count), self.reducer.grad_scale,
+                                      ptr(self.clip_out) if norm else None, ptr(watch), ptr(self.guard) if guarded else None,
+                                      ptr(state), None if state is None else ptr(self.rbackup), 0 if state is None else state.numel(),
+                                      None if ema is None else ptr(ema.shadow), 0.0 if ema is None else ema.decay, stream()),
+              "otvae_adam_step_ema")
 
     @property
     def skipped_steps(self) -> int:
         """steps the device-side guard refused so far (one host read)"""
         return int(self.guard[0].item())
 
-    def _allreduce(self):
-        self.reducer.allreduce()
-
     def _eager_step(self):
         if self.dp_overlap:
-            logs = self._phase1()
+            logs = self._forward_backward(cut=True)
             self.reducer.allreduce_range(*self._dec_range, wait=False)  # flies under phase 2
             self._phase2()
             self._allreduce_split_tail()
         else:
             logs = self._forward_backward()
-            self._allreduce()
+            self.reducer.allreduce()
         self._adam()
         return logs
 
@@ -537,37 +498,19 @@ class HipTrainer:
         if self._captured or not self.use_graph:
             return
         self._gs.release()   # (graphs of an earlier attempt that raised half-way)
-        snap = (self.pflat.clone(), self.m.clone(), self.v.clone(), self.step_count.clone(), self.guard.clone())
-        # everything else a step mutates: every buffer of the model (BatchNorm running statistics, EMA embeddings of a
-        # ConditionalGaussianPrior ...), parameters outside the flat buffer (frozen ones an EMA rewrites), the dropout
-        # key counters, and the running statistics of the latent operator (which may hold earlier eager steps' samples)
-        flat_ids = {id(p) for p in self.params}
-        state = [t for t in self.model.buffers()] + [p.data for p in self.model.parameters() if id(p) not in flat_ids]
-        state += [mod.__dict__["_dropout_key"] for mod in self.model.modules() if isinstance(mod.__dict__.get("_dropout_key"), Tensor)]
-        if self.latent_stats is not None:
-            state += [t for t in self.latent_stats.buffers()] + [p.data for p in self.latent_stats.parameters()]
+        # the warm-up / capture must not count as training: everything a step writes is put back afterwards
+        state = self._step_state() + [self.pflat, self.m, self.v, self.step_count, self.guard]
         if self.ema is not None:
             state.append(self.ema.shadow)
-        state_snap = [t.clone() for t in state]
-        s = _lib.fresh_stream(self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self._eager_step()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        # "thread_local": only this thread's calls are policed while the stream captures.  Under the default ("global")
-        # an event query from another thread -- the RCCL watchdog polling the collectives of earlier steps -- is an
-        # illegal call that kills the capture, and the process with it, whenever the poll happens to land inside it
-        mode = dict(capture_error_mode=os.environ.get("OTVAE_CAPTURE_ERROR_MODE", "thread_local"))
-        gs = self._gs
-        mode["stream"] = _lib.fresh_stream(self.device)   # a capture stream nothing else of this process aliases (_lib.fresh_stream)
+        snap = snapshot(state)
+        warm_up(self.device, self._eager_step, warmup)
+        gs, mode = self._gs, capture_kwargs(self.device)
         # capture_guard: graphs parked by engines that died inside an earlier capture are destroyed first, and the cyclic collector
         # stays off until the capture ends (a graph destroyed inside an open capture aborts the process: engine/lifetime.py)
         with capture_guard():
             if self.dp_overlap:
                 with torch.cuda.graph(gs.new("fb"), **mode):
-                    logs = self._phase1()
+                    logs = self._forward_backward(cut=True)
                     self._out_static = self._loss_vector(logs)
                 pool = gs.get("fb").pool()
                 with torch.cuda.graph(gs.new("b2"), pool=pool, **mode):  # the cut tensors live in graph 1's pool
@@ -600,12 +543,7 @@ class HipTrainer:
                     self._out_static = self._loss_vector(logs)
                 with torch.cuda.graph(gs.new("opt"), **mode):
                     self._adam()
-        # the warm-up/capture must not count as training: restore parameters, moments, step and BN buffers
-        with torch.no_grad():
-            self.pflat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2]); self.step_count.copy_(snap[3])
-            self.guard.copy_(snap[4])
-            for t, v in zip(state, state_snap):
-                t.copy_(v)
+        restore(state, snap)
         torch.cuda.synchronize()
         self._captured = True
 
@@ -620,8 +558,6 @@ class HipTrainer:
 
     def _draw_eps(self) -> None:
         """re-parametrisation noise of the next step from the device-side generator (one launch of this library)"""
-        from .. import functional as HF
-        from ..utils import hasarg
         if self._rng_key is None:
             self._rng_key = HF.new_rng_key(self.device)
             prior = getattr(self.model, "prior", None)
@@ -651,7 +587,7 @@ class HipTrainer:
                 self._allreduce_split_tail()
                 gs.get("opt").replay()
             elif gs.get("opt") is not None:
-                self._allreduce()
+                self.reducer.allreduce()
                 gs.get("opt").replay()
             out = self._out_static
         else:
@@ -674,11 +610,7 @@ class HipTrainer:
         if self.reducer.stream is not None:
             self.reducer.stream.synchronize()
         self._gs.release()
-        self._out_static = None
-        self._cut = None
-        self._logs = None
-        self.latents = None
-        self._watch = None
+        self._out_static = self._cut = self._logs = self._watch = self.latents = None
         model = self._model_ref()
         if model is not None and hasattr(model, "_last_cut"):
             model._last_cut = None
