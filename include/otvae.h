@@ -701,6 +701,34 @@ int otvae_codebook_kmeans(const float* x, const int64_t* idx, int nb, int B, int
 int otvae_gmm_diag_energy(int dtype, const void* x, const void* mean, const void* var, const void* logw, int nb, int B, int K,
                           int d, void* energy, void* stream);
 
+/* ---- Discrete Auto Diffuser (model/discrete_auto_diffuser.py) ------------------------------------------------------------------------ */
+/* DAD.prior_loss's cross-entropy (discrete_auto_diffuser.py:63-72: two sliced copies, two transposes, F.cross_entropy with soft labels,
+ * sum over the tokens) in one pass: loss[b] = sum_{t < T-1} ( -sum_k probs[b][t+1][k] * log_softmax(logits[b][t][:])[k] ), the
+ * one-token shift done by index arithmetic.  logits / probs: fp32 [B][T][K] addressed as base + b * stride_b + t * stride_t + k (strides in
+ * elements, rows of K contiguous values; read only, so a transposed or broadcast view is taken in place).  Also written, for the backward pass: lse[B][T] (log-sum-exp of row (b, t)) and psum[B][T]
+ * (sum_k probs[b][t+1][k]); their column T-1 is 0.  ws: otvae_soft_ce_ws(B, T) bytes, 8-byte aligned.  Fixed reduction orders, the sums
+ * in fp64.  T < 2 or K < 1: OTVAE_EUNSUPPORTED. */
+int64_t otvae_soft_ce_ws(int B, int T);
+int otvae_soft_ce_fwd(const float* logits, int64_t logits_stride_b, int64_t logits_stride_t, const float* probs,
+                      int64_t probs_stride_b, int64_t probs_stride_t, int B, int T, int K, float* loss, float* lse, float* psum,
+                      void* ws, void* stream);
+/* Its backward pass (what autograd derives from discrete_auto_diffuser.py:63-72), gloss [B]: dlogits[b][t][k] = gloss[b] *
+ * (exp(logits[b][t][k] - lse[b][t]) * psum[b][t] - probs[b][t+1][k]) for t < T-1 and exactly 0 in row T-1; dprobs[b][t+1][k] =
+ * -gloss[b] * (logits[b][t][k] - lse[b][t]) and exactly 0 in row 0.  dlogits / dprobs: contiguous [B][T][K], either may be NULL. */
+int otvae_soft_ce_bwd(const float* logits, int64_t logits_stride_b, int64_t logits_stride_t, const float* probs,
+                      int64_t probs_stride_b, int64_t probs_stride_t, const float* lse, const float* psum, const float* gloss, int B,
+                      int T, int K, float* dlogits, float* dprobs, void* stream);
+/* One step of DAD.sample's loop (discrete_auto_diffuser.py:88-89: Categorical(logits[:, i].softmax(-1)).sample()):
+ * ids[b][col] = the number of k whose cumulative sum of exp(logits[b][pos][0..k] - max) is <= u[b] * total, clamped to K-1 -- the inverse
+ * CDF of u[b] under softmax(logits[b][pos][:]), exp and the scan in fp64 in index order.  logits: fp32, row (b, pos) at base + b * stride_b +
+ * pos * stride_t; u [B] in [0, 1), or NULL: drawn from the library's counter-based generator, key = device int64[2] {seed, call counter}
+ * (the draw depends on (key, col, b) only; the caller advances the counter).  ids: int64 [B][T] with row stride ids_stride. */
+int otvae_categorical_sample(const float* logits, int64_t stride_b, int64_t stride_t, int pos, int B, int K, const float* u,
+                             const int64_t* key, int64_t* ids, int64_t ids_stride, int T, int col, void* stream);
+/* The decode of sampled ids (discrete_auto_diffuser.py:92-93: one_hot(ids) @ codebook, B*T*K*d multiply-adds for a row gather):
+ * out[n][:] = codebook[ids[n]][:], codebook [K][d], ids [N] int64; an id outside [0, K) yields a NaN row. */
+int otvae_codebook_gather(const float* codebook, const int64_t* ids, int64_t N, int K, int d, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

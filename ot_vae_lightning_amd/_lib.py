@@ -195,6 +195,11 @@ SIGNATURES = {
     "otvae_codebook_energy": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, vp, vp]),
     "otvae_codebook_energy_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp]),
     "otvae_codebook_kmeans": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "otvae_soft_ce_ws": (i64, [i32, i32]),
+    "otvae_soft_ce_fwd": (i32, [vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "otvae_soft_ce_bwd": (i32, [vp, i64, i64, vp, i64, i64, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "otvae_categorical_sample": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, i64, i32, i32, vp]),
+    "otvae_codebook_gather": (i32, [vp, vp, i64, i32, i32, vp, vp]),
 }
 
 

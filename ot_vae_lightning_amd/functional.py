@@ -2065,3 +2065,70 @@ def conv_bn_act(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, gamma:
                                                                         num_batches_tracked, training)
     return torch.ops.otvae.conv_bn_act(x, weight, bias, gamma, beta, mean, invstd, scale, shift, residual, stride, pad, up, relu,
                                        training)
+
+
+# ------------------------------------------------------------------------------------------------ Discrete Auto Diffuser
+def soft_cross_entropy(logits: Tensor, probs: Tensor) -> Tensor:
+    """ce[B] of ``DAD.prior_loss`` (reference model/discrete_auto_diffuser.py:63-72): the soft-label cross-entropy between
+    ``logits[:, :-1]`` and ``probs[:, 1:]`` ([B, T, K] each), summed over the tokens; one pass, no shifted copies
+    (``torch.ops.otvae.soft_cross_entropy``).  Differentiable in both arguments."""
+    return torch.ops.otvae.soft_cross_entropy(logits, probs)[0]
+
+
+@torch.no_grad()
+def categorical_sample_(ids: Tensor, col: int, logits: Tensor, pos: int, u: Optional[Tensor] = None,
+                        key: Optional[Tensor] = None) -> Tensor:
+    """``ids[:, col] = Categorical(logits[:, pos].softmax(-1)).sample()`` in place (reference model/discrete_auto_diffuser.py:88-89) as
+    the inverse CDF of one uniform per row: ``u`` [B] in [0, 1), or drawn on the device from ``key`` (``new_dropout_key``: int64
+    {seed, call counter}; the draw depends on (key, col, row) only).  ids: int64 [B, T]; logits: float32 [B, *, K].  No host read."""
+    _lib.require_cuda(logits, "logits")
+    if ids.dim() != 2 or ids.dtype != torch.int64 or ids.stride(1) != 1:
+        raise ValueError("categorical_sample_ writes into an int64 [B, T] id matrix with unit column stride")
+    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.shape[0] != ids.shape[0]:
+        raise ValueError(f"categorical_sample_ takes float32 [B, T, K] logits, got {tuple(logits.shape)} {logits.dtype}")
+    if logits.stride(2) != 1:
+        logits = logits.contiguous()
+    if not 0 <= pos < logits.shape[1]:
+        raise ValueError(f"position {pos} outside the {logits.shape[1]} rows of logits")
+    if u is None and key is None:
+        raise ValueError("categorical_sample_ needs the uniforms `u` or a generator `key`")
+    if u is not None:
+        u = u.to(torch.float32).contiguous()
+        if u.shape != (ids.shape[0],):
+            raise ValueError(f"`u` must hold one uniform per row ({ids.shape[0]}), got {tuple(u.shape)}")
+    b, t = ids.shape
+    check(_lib.load().otvae_categorical_sample(ptr(logits), logits.stride(0), logits.stride(1), int(pos), b, logits.shape[2], ptr(u),
+                                               ptr(key), ptr(ids), ids.stride(0), t, int(col), stream()), "otvae_categorical_sample")
+    return ids
+
+
+class _CodebookGatherFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, codebook, ids):
+        k, d = codebook.shape
+        flat = ids.reshape(-1).contiguous()
+        out = torch.empty((flat.numel(), d), device=codebook.device, dtype=torch.float32)
+        check(_lib.load().otvae_codebook_gather(ptr(codebook), ptr(flat), flat.numel(), k, d, ptr(out), stream()), "otvae_codebook_gather")
+        ctx.save_for_backward(flat)
+        ctx.k = k
+        return out.reshape(*ids.shape, d)
+
+    @staticmethod
+    def backward(ctx, g):
+        (flat,) = ctx.saved_tensors
+        d = g.shape[-1]
+        gw = torch.empty((ctx.k, d), device=g.device, dtype=torch.float32)
+        check(_lib.load().otvae_embedding_bwd(ptr(g.reshape(-1, d).contiguous().float()), ptr(flat), flat.numel(), ctx.k, d, ptr(gw),
+                                              stream()), "otvae_embedding_bwd")
+        return gw, None
+
+
+def codebook_gather(codebook: Tensor, ids: Tensor) -> Tensor:
+    """``codebook[ids]`` ([K, d] float32, int64 ids of any shape -> [*ids.shape, d]): what the reference computes as
+    ``one_hot(ids) @ codebook`` (model/discrete_auto_diffuser.py:92-93), as a row gather (``otvae_codebook_gather``)."""
+    _lib.require_cuda(codebook, "codebook")
+    if codebook.dim() != 2 or codebook.dtype != torch.float32 or ids.dtype != torch.int64:
+        raise ValueError(f"codebook_gather takes a float32 [K, d] codebook and int64 ids, got {tuple(codebook.shape)} {codebook.dtype} / {ids.dtype}")
+    if ids.numel() == 0:
+        return codebook.new_empty((*ids.shape, codebook.shape[1]))
+    return _CodebookGatherFn.apply(codebook.contiguous(), ids)

@@ -1,2 +1,3 @@
 from .base import *  # noqa: F401,F403
 from .vae import *  # noqa: F401,F403
+from .discrete_auto_diffuser import *  # noqa: F401,F403

@@ -100,10 +100,16 @@ class VAE(VisionModule):
     def prior_loss(self, prior_loss: Tensor, prior_artifacts, **kwargs) -> Tensor:
         return prior_loss.mean()
 
+    def per_sample_prior_loss(self, prior_loss: Tensor, prior_artifacts, **kwargs) -> Tensor:
+        """The [B] vector whose mean ``prior_loss`` returns: the fused reduction of ``nelbo`` takes it per sample.  A subclass that adds
+        terms of its own to the prior's regulariser (``DAD``: the reference overrides ``prior_loss``) adds them here."""
+        return prior_loss
+
     def nelbo(self, batch: Batch, batch_idx: int) -> Tuple[Tensor, Dict[str, Tensor], Batch]:
         samples, target, kwargs = batch["samples"], batch["target"], batch["kwargs"]
         batch_size = samples.size(0)
         latents, prior_loss, prior_artifacts = self.encode(samples, expand=True, return_prior_artifacts=True, **kwargs)
+        prior_loss = self.per_sample_prior_loss(prior_loss, prior_artifacts)
         reconstructions = self.decode(latents, expand_kwargs=True, **kwargs)
         reconstructions_mean = self._reduce_mean(reconstructions)
         out3 = HF.nelbo_loss(reconstructions_mean, target, prior_loss)   # [total, recon, prior/(C*H*W)]

@@ -11,11 +11,13 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
     otvae::sinkhorn_prior           sq. euclidean cost -> sinkhorn_log -> <C,pi> ot/w2_utils.py:265-269,276-319
     otvae::gaussian_w2_prior        _stats -> mean_cov -> w2_gaussian            gaussian_model.py:144-157, matrix_utils.py:145-158,
                                                                                  w2_utils.py:40-80
+    otvae::soft_cross_entropy       DAD.prior_loss's shifted soft-label CE       model/discrete_auto_diffuser.py:63-72
 
     otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
     otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
 
-The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the two OT priors).
+The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the two OT priors,
+``soft_cross_entropy``).
 ``ConvBlock`` runs its two branches and the training engine's in-place gradient slots through the packed variant of the
 same kernels (``functional.conv_layers``); ``otvae::conv_bn_act`` is the single-layer functional form.
 """
@@ -31,7 +33,8 @@ from ._lib import check, ptr, stream
 
 __all__ = ["OPS"]
 
-OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior")
+OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior",
+       "soft_cross_entropy")
 _lib_def = torch.library.Library("otvae", "DEF")
 
 
@@ -451,6 +454,71 @@ def _w2_backward(ctx, g, _gmu, _gq, _gvt):
 
 
 torch.library.register_autograd("otvae::gaussian_w2_prior", _w2_backward, setup_context=_w2_setup)
+
+
+# ------------------------------------------------------------------------------------------------ DAD's shifted soft-label CE
+def _rows_k(t: Tensor, name: str) -> Tensor:
+    """[B, T, K] fp32 on the device with rows of K contiguous values (any batch / token strides: a transposed view is read in place)"""
+    _lib.require_cuda(t, name)
+    if t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError(f"soft_cross_entropy takes float32 [B, T, K] tensors, got {name} {tuple(t.shape)} {t.dtype}")
+    if t.stride(2) != 1:
+        t = t.contiguous()
+    return t
+
+
+def _sce_fwd(logits: Tensor, probs: Tensor):
+    lib = _lib.load()
+    logits, probs = _rows_k(logits, "logits"), _rows_k(probs, "probs")
+    if logits.shape != probs.shape:
+        raise ValueError(f"soft_cross_entropy: logits {tuple(logits.shape)} and probs {tuple(probs.shape)} differ in shape")
+    b, t, k = logits.shape
+    loss = torch.empty(b, device=logits.device, dtype=torch.float32)
+    lse = torch.empty((b, t), device=logits.device, dtype=torch.float32)
+    psum = torch.empty((b, t), device=logits.device, dtype=torch.float32)
+    ws = torch.empty(max(1, lib.otvae_soft_ce_ws(b, t) // 8), device=logits.device, dtype=torch.float64)
+    check(lib.otvae_soft_ce_fwd(ptr(logits), logits.stride(0), logits.stride(1), ptr(probs), probs.stride(0), probs.stride(1), b, t, k,
+                                ptr(loss), ptr(lse), ptr(psum), ptr(ws), stream()), "otvae_soft_ce_fwd")
+    return loss, lse, psum
+
+
+def _sce_bwd(gloss: Tensor, logits: Tensor, probs: Tensor, lse: Tensor, psum: Tensor, need_dlogits: bool, need_dprobs: bool):
+    lib = _lib.load()
+    logits, probs = _rows_k(logits, "logits"), _rows_k(probs, "probs")
+    b, t, k = logits.shape
+    e = logits.new_empty(0)
+    dl = torch.empty((b, t, k), device=logits.device, dtype=torch.float32) if need_dlogits else None
+    dp = torch.empty((b, t, k), device=logits.device, dtype=torch.float32) if need_dprobs else None
+    check(lib.otvae_soft_ce_bwd(ptr(logits), logits.stride(0), logits.stride(1), ptr(probs), probs.stride(0), probs.stride(1),
+                                ptr(lse.contiguous()), ptr(psum.contiguous()), ptr(gloss.float().contiguous()), b, t, k, ptr(dl), ptr(dp),
+                                stream()), "otvae_soft_ce_bwd")
+    return (dl if dl is not None else e), (dp if dp is not None else e)
+
+
+_define("soft_cross_entropy", "(Tensor logits, Tensor probs) -> (Tensor, Tensor, Tensor)", _sce_fwd,
+        lambda logits, probs: (logits.new_empty(logits.shape[0]), logits.new_empty(logits.shape[:2]), logits.new_empty(logits.shape[:2])))
+_define("soft_cross_entropy_backward", "(Tensor gloss, Tensor logits, Tensor probs, Tensor lse, Tensor psum, bool need_dlogits, "
+        "bool need_dprobs) -> (Tensor, Tensor)", _sce_bwd,
+        lambda gloss, logits, probs, lse, psum, need_dlogits, need_dprobs: (
+            logits.new_empty(tuple(logits.shape) if need_dlogits else (0,)), logits.new_empty(tuple(logits.shape) if need_dprobs else (0,))))
+
+
+def _sce_setup(ctx, inputs, output):
+    logits, probs = inputs
+    ctx.save_for_backward(logits, probs, output[1], output[2])
+    ctx.set_materialize_grads(False)  # lse / psum never carry a gradient
+
+
+def _sce_backward(ctx, gloss, _glse, _gpsum):
+    need_dl, need_dp = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if gloss is None or not (need_dl or need_dp):
+        return None, None
+    logits, probs, lse, psum = ctx.saved_tensors
+    dl, dp = torch.ops.otvae.soft_cross_entropy_backward(gloss, logits, probs, lse, psum, need_dl, need_dp)
+    return (dl if need_dl else None), (dp if need_dp else None)
+
+
+torch.library.register_autograd("otvae::soft_cross_entropy", _sce_backward, setup_context=_sce_setup)
 
 
 # ------------------------------------------------------------------------------------------------ validation metrics

@@ -274,8 +274,8 @@ class CodebookModel(DistributionModel):
         generator, so they are not comparable across devices); the deterministic nearest-atom indices are
         ``nearest(samples)[1]``."""
         probs = self.assignment_probs(samples)
-        distribution = D.Categorical(probs)
-        indices = distribution.sample()
+        distribution = self._categorical(probs)
+        indices = self._draw_indices(distribution)
         mode = self.mode
         if mode == "mean" or self.topk == 1:   # (base.py:228: with one atom left the soft weights are the one-hot weights)
             weights = probs
@@ -289,14 +289,35 @@ class CodebookModel(DistributionModel):
             weights = F.one_hot(idx, self.n_components).type_as(probs)
         return weights, indices, distribution
 
+    @staticmethod
+    def _categorical(probs: Tensor) -> D.Categorical:
+        """``D.Categorical(probs)``; its argument validation reads the device, which a stream under graph capture cannot do"""
+        if probs.is_cuda and torch.cuda.is_current_stream_capturing():
+            return D.Categorical(probs, validate_args=False)
+        return D.Categorical(probs)
+
+    def _draw_indices(self, distribution: D.Categorical) -> Tensor:
+        """``distribution.sample()``; with uniforms injected as ``self.index_noise`` ([*, B] in [0, 1), used once, like
+        ``gumbel_noise``) the draw is their inverse CDF under the assignment probabilities (``otvae_categorical_sample``), so a
+        recorded draw can be reproduced."""
+        noise, self.index_noise = getattr(self, "index_noise", None), None
+        if noise is None:
+            return distribution.sample()
+        from ... import functional as HF
+        probs = distribution.probs.detach()
+        k = probs.shape[-1]
+        ids = torch.empty((probs.numel() // k, 1), device=probs.device, dtype=torch.int64)
+        HF.categorical_sample_(ids, 0, probs.float().log().reshape(-1, 1, k), 0, u=noise.reshape(-1))
+        return ids.reshape(probs.shape[:-1])
+
     def predict(self, features: Tensor):
         """(weights @ codebook, sampled indices, assignment distribution) -- codebook_model.py:145-148.  In 'argmax'
         mode the product with a one-hot matrix is the gather the assignment kernel already did."""
         self._validate_samples(features)
         if self.mode == "argmax" and not self.update_with_autograd and self.topk != 1:
             preds, _ = self._argmax(features)
-            distribution = D.Categorical(self.assignment_probs(features))
-            return preds.type_as(self.codebook), distribution.sample(), distribution
+            distribution = self._categorical(self.assignment_probs(features))
+            return preds.type_as(self.codebook), self._draw_indices(distribution), distribution
         weights, indices, distribution = self.assign(features)
         return mm(weights.type_as(self.codebook), self.codebook), indices, distribution
 
