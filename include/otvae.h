@@ -729,6 +729,26 @@ int otvae_categorical_sample(const float* logits, int64_t stride_b, int64_t stri
  * out[n][:] = codebook[ids[n]][:], codebook [K][d], ids [N] int64; an id outside [0, K) yields a NaN row. */
 int otvae_codebook_gather(const float* codebook, const int64_t* ids, int64_t N, int K, int d, float* out, void* stream);
 
+/* ---- key/value-cached decoding of the causal AutoRegressive transformer (networks/vit.py:249-260), one new token per row ------------- */
+/* One post-norm nn.TransformerEncoderLayer (ReLU, eval mode, causal mask) for the token at position pos of each of B rows, as ONE launch:
+ *   qkv = x w_in + b_in (nn.MultiheadAttention's q | k | v split, heads contiguous);  kcache[b][h][pos][:] = k, vcache[b][h][pos][:] = v;
+ *   a = softmax(q . kcache[b][h][0..pos][:]^T / sqrt(C)) . vcache[b][h][0..pos][:];  x1 = LayerNorm1(x + a w_out + b_out);
+ *   y = LayerNorm2(x1 + relu(x1 w1 + b1) w2 + b2).
+ * x, y: [B][D] (y may not alias x).  Weights on [in][out] memory: w_in [D][3D], w_out [D][D], w1 [D][F], w2 [F][D].  LayerNorms: biased
+ * variance, eps1 / eps2.  kcache / vcache: fp32 [B][H][Tmax][C], C = D / H, 16-byte aligned; rows 0 .. pos-1 are read, row pos is written,
+ * nothing beyond pos is touched.  No atomics: bit-reproducible.
+ * OTVAE_EINVAL: null pointers, pos >= Tmax, D % H != 0.  OTVAE_EUNSUPPORTED outside the envelope 16 <= D <= 512 with D % 16 == 0,
+ * C % 4 == 0, F <= 4 D, Tmax <= 4096 (the layer's activations of 16 rows stay in LDS: 64 (4 D + 8) bytes). */
+int otvae_ar_layer_step(const float* x, int B, int D, int H, int F, int pos, int Tmax, const float* w_in, const float* b_in,
+                        const float* w_out, const float* b_out, const float* ln1_g, const float* ln1_b, float eps1, const float* w1,
+                        const float* b1, const float* w2, const float* b2, const float* ln2_g, const float* ln2_b, float eps2,
+                        float* kcache, float* vcache, float* y, void* stream);
+/* The step's input (networks/vit.py:249-260 with PositionalEmbedding, vit.py:33-58, restricted to one position):
+ * out[b][:] = LayerNorm(vocab[ids[b * ids_stride]][:] + positions[pos][:]), vocab [V][D], positions [P][D], out [B][D]; an id outside
+ * [0, V) yields a NaN row.  ids_stride in elements: a column of an int64 [B][T] matrix is taken in place. */
+int otvae_ar_embed_step(const int64_t* ids, int64_t ids_stride, int pos, int B, int D, int V, int P, const float* vocab,
+                        const float* positions, const float* ln_g, const float* ln_b, float eps, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

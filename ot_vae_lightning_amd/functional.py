@@ -2132,3 +2132,88 @@ def codebook_gather(codebook: Tensor, ids: Tensor) -> Tensor:
     if ids.numel() == 0:
         return codebook.new_empty((*ids.shape, codebook.shape[1]))
     return _CodebookGatherFn.apply(codebook.contiguous(), ids)
+
+
+# ------------------------------------------------------------------------------------------------ key/value-cached decoding
+def _no_grad_inputs(who: str, *tensors: Optional[Tensor]) -> None:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{who} has no backward pass: call it under torch.no_grad() or with tensors that do not require grad")
+
+
+def _dense_f32(t: Tensor, name: str, shape: Tuple[int, ...]) -> None:
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"`{name}` must be a contiguous float32 {list(shape)} tensor, got {list(t.shape)} {t.dtype} "
+                         f"(contiguous: {t.is_contiguous()})")
+
+
+def _linear_memory(w: Tensor, name: str, d_out: int, d_in: int) -> Tensor:
+    """the [d_in][d_out] memory of a logical [d_out, d_in] Linear weight (``new_linear_weight``), without a copy"""
+    if w.dtype != torch.float32 or tuple(w.shape) != (d_out, d_in) or not w.t().is_contiguous():
+        raise ValueError(f"`{name}` must be a float32 [{d_out}, {d_in}] weight on [in][out] memory (new_linear_weight), got "
+                         f"{list(w.shape)} {w.dtype} with strides {w.stride()}")
+    return w
+
+
+def ar_embed_step(ids_col: Tensor, pos: int, vocab: Tensor, positions: Tensor, ln_weight: Tensor, ln_bias: Tensor, eps: float) -> Tensor:
+    """``LayerNorm(vocab[ids_col] + positions[pos])`` -> [B, D]: the input of one decoding step (``AutoRegressive``'s vocabulary
+    embedding and ``PositionalEmbedding`` at one position) as one launch (``otvae_ar_embed_step``).  ids_col: int64 [B], any stride (a
+    column of the id matrix is read in place).  No backward pass."""
+    _lib.require_cuda(vocab, "vocab")
+    _lib.require_cuda(ids_col, "ids_col")
+    _no_grad_inputs("ar_embed_step", vocab, positions, ln_weight, ln_bias)
+    if ids_col.dim() != 1 or ids_col.dtype != torch.int64 or ids_col.numel() == 0:
+        raise ValueError(f"`ids_col` must be a non-empty int64 [B] tensor, got {list(ids_col.shape)} {ids_col.dtype}")
+    if vocab.dim() != 2 or positions.dim() != 2:
+        raise ValueError("`vocab` and `positions` must be [V, D] and [P, D]")
+    (v, d), p = vocab.shape, positions.shape[0]
+    _dense_f32(vocab, "vocab", (v, d))
+    _dense_f32(positions, "positions", (p, d))
+    _dense_f32(ln_weight, "ln_weight", (d,))
+    _dense_f32(ln_bias, "ln_bias", (d,))
+    b = ids_col.shape[0]
+    out = torch.empty((b, d), device=vocab.device, dtype=torch.float32)
+    check(_lib.load().otvae_ar_embed_step(ptr(ids_col), ids_col.stride(0), int(pos), b, d, v, p, ptr(vocab), ptr(positions), ptr(ln_weight),
+                                          ptr(ln_bias), float(eps), ptr(out), stream()), "otvae_ar_embed_step")
+    return out
+
+
+def ar_layer_step(x: Tensor, pos: int, heads: int, in_proj_weight: Tensor, in_proj_bias: Tensor, out_proj_weight: Tensor,
+                  out_proj_bias: Tensor, norm1_weight: Tensor, norm1_bias: Tensor, eps1: float, linear1_weight: Tensor,
+                  linear1_bias: Tensor, linear2_weight: Tensor, linear2_bias: Tensor, norm2_weight: Tensor, norm2_bias: Tensor,
+                  eps2: float, kcache: Tensor, vcache: Tensor) -> Tensor:
+    """One post-norm ``nn.TransformerEncoderLayer`` (ReLU, eval mode, causal) for the token at position ``pos`` of every row, as one
+    launch (``otvae_ar_layer_step``): x [B, D] -> y [B, D]; the token's key / value rows are appended to ``kcache`` / ``vcache``
+    (float32 [B, H, Tmax, D / H], rows < pos are read, nothing beyond pos is touched).  The weights are the layer's parameters as
+    they are (logical [out, in] on [in][out] memory).  No backward pass; a shape outside the kernel's envelope raises
+    ``NotImplementedError``."""
+    _lib.require_cuda(x, "x")
+    _lib.require_cuda(kcache, "kcache")
+    _no_grad_inputs("ar_layer_step", x, in_proj_weight, in_proj_bias, out_proj_weight, out_proj_bias, norm1_weight, norm1_bias,
+                    linear1_weight, linear1_bias, linear2_weight, linear2_bias, norm2_weight, norm2_bias)
+    if x.dim() != 2:
+        raise ValueError(f"`x` must be [B, D], got {list(x.shape)}")
+    b, d = x.shape
+    h, f = int(heads), linear1_weight.shape[0]
+    if h < 1 or d % h:
+        raise ValueError(f"D = {d} is not a multiple of {h} heads")
+    _dense_f32(x, "x", (b, d))
+    _linear_memory(in_proj_weight, "in_proj_weight", 3 * d, d)
+    _linear_memory(out_proj_weight, "out_proj_weight", d, d)
+    _linear_memory(linear1_weight, "linear1_weight", f, d)
+    _linear_memory(linear2_weight, "linear2_weight", d, f)
+    _dense_f32(in_proj_bias, "in_proj_bias", (3 * d,))
+    _dense_f32(linear1_bias, "linear1_bias", (f,))
+    for name, t in (("out_proj_bias", out_proj_bias), ("norm1_weight", norm1_weight), ("norm1_bias", norm1_bias),
+                    ("linear2_bias", linear2_bias), ("norm2_weight", norm2_weight), ("norm2_bias", norm2_bias)):
+        _dense_f32(t, name, (d,))
+    if kcache.dim() != 4 or kcache.shape != vcache.shape:
+        raise ValueError(f"the caches must be two [B, H, Tmax, C] tensors, got {list(kcache.shape)} / {list(vcache.shape)}")
+    tmax = kcache.shape[2]
+    _dense_f32(kcache, "kcache", (b, h, tmax, d // h))
+    _dense_f32(vcache, "vcache", (b, h, tmax, d // h))
+    y = torch.empty_like(x)
+    check(_lib.load().otvae_ar_layer_step(ptr(x), b, d, h, f, int(pos), tmax, ptr(in_proj_weight), ptr(in_proj_bias), ptr(out_proj_weight),
+                                          ptr(out_proj_bias), ptr(norm1_weight), ptr(norm1_bias), float(eps1), ptr(linear1_weight),
+                                          ptr(linear1_bias), ptr(linear2_weight), ptr(linear2_bias), ptr(norm2_weight), ptr(norm2_bias),
+                                          float(eps2), ptr(kcache), ptr(vcache), ptr(y), stream()), "otvae_ar_layer_step")
+    return y

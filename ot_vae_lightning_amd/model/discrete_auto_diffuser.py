@@ -56,11 +56,21 @@ class DAD(VAE):
         return super().prior_loss(self.per_sample_prior_loss(prior_loss, artifacts, **kwargs), artifacts, **kwargs)
 
     @VAE.postprocess
-    def sample(self, batch_size: int, *, init_indices: Optional[Tensor] = None, noise: Optional[Tensor] = None, **kwargs) -> Tensor:
+    def sample(self, batch_size: int, *, init_indices: Optional[Tensor] = None, noise: Optional[Tensor] = None, cached: bool = False,
+               **kwargs) -> Tensor:
         """Reference discrete_auto_diffuser.py:77-95.  ``init_indices`` (int64 [B, T], the uniformly random start; only column 0
         survives) and ``noise`` ([B, T - 1] uniforms in [0, 1): token i + 1 is the inverse CDF of ``noise[:, i]`` under the decoder's
-        distribution at position i) make the draw reproducible; without them both are drawn on the device."""
+        distribution at position i) make the draw reproducible; without them both are drawn on the device.
+
+        ``cached=True`` advances the decoder one token at a time on per-layer key / value caches (``AutoRegressive.decode_state`` /
+        ``step``) instead of running it on the whole id matrix T - 1 times: same draws, same distribution at every position.  A decoder
+        that route cannot take (``decode_state``'s rules) raises ``NotImplementedError``; there is no silent fall-back."""
         device, T = self.device, self.n_tokens
+        state = None
+        if cached:
+            if not hasattr(self.autoregressive_decoder, "decode_state"):
+                raise NotImplementedError(f"`cached=True` needs a decoder with `decode_state` / `step`, got {type(self.autoregressive_decoder).__name__}")
+            state = self.autoregressive_decoder.decode_state(batch_size, T)
         if init_indices is None:
             embed_ind = torch.randint(high=self.num_embeddings, size=(batch_size, T), device=device)
         else:
@@ -79,8 +89,11 @@ class DAD(VAE):
             noise = noise.to(device=device, dtype=torch.float32).t().contiguous()   # [T - 1, B]: one contiguous row per step
         with torch.no_grad():
             for i in range(T - 1):
-                logits = self.autoregressive_decoder(embed_ind)
-                HF.categorical_sample_(embed_ind, i + 1, logits, i, u=None if noise is None else noise[i], key=key)
+                if state is not None:
+                    logits, at = self.autoregressive_decoder.step(embed_ind[:, i], state).unsqueeze(1), 0
+                else:
+                    logits, at = self.autoregressive_decoder(embed_ind), i
+                HF.categorical_sample_(embed_ind, i + 1, logits, at, u=None if noise is None else noise[i], key=key)
             codebook = self.prior.codebook_model.codebook
             latents = HF.codebook_gather(codebook.reshape(-1, codebook.shape[-1]).float(), embed_ind).type_as(codebook)
         latents = self.prior.unflatten_and_unpermute(latents.transpose(0, 1))

@@ -363,7 +363,7 @@ class CNN(FilterSequential):
 
 class AutoEncoder(nn.Module):
     """encoder CNN + mirrored decoder CNN with ``encode``/``decode``/``latent_size`` (reference cnn.py:463-600).
-    Class/time conditioning feeds FiLM embeddings, which the MI355X ConvLayer does not implement."""
+    Class/time conditioning feeds FiLM embeddings, which the MI355X ConvLayer applies through ``_film``."""
 
     def __init__(self, in_features: int, latent_features: int, in_resolution: Optional[int] = None,
                  latent_resolution: Optional[int] = None, intermediate_features: Optional[List[int]] = None,

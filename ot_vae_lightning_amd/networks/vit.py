@@ -30,7 +30,8 @@ from torch import Tensor
 
 from .. import functional as HF
 
-__all__ = ["PositionalEmbedding", "ViT", "AutoRegressive", "TokenLinear", "TokenLayerNorm", "TokenEncoderLayer", "TokenDecoderLayer"]
+__all__ = ["PositionalEmbedding", "ViT", "AutoRegressive", "ARDecodeState", "TokenLinear", "TokenLayerNorm", "TokenEncoderLayer",
+           "TokenDecoderLayer"]
 
 
 def pair(t):
@@ -400,9 +401,29 @@ class ViT(nn.Module):
         return self.embed_to_patch(out)
 
 
+class ARDecodeState:
+    """What ``AutoRegressive.step`` carries from one token to the next: per transformer layer the keys and values of the tokens seen so
+    far (float32 [B, heads, max_tokens, dim / heads]) and ``length``, the number of tokens consumed = the position of the next one.
+    ``reset()`` starts a new sequence in the same memory (nothing beyond ``length`` is ever read, so the caches are not cleared)."""
+    __slots__ = ("batch_size", "max_tokens", "length", "kcache", "vcache")
+
+    def __init__(self, batch_size: int, max_tokens: int, depth: int, heads: int, width: int, device):
+        self.batch_size, self.max_tokens, self.length = batch_size, max_tokens, 0
+        self.kcache = [torch.empty((batch_size, heads, max_tokens, width), device=device, dtype=torch.float32) for _ in range(depth)]
+        self.vcache = [torch.empty_like(k) for k in self.kcache]
+
+    def reset(self) -> "ARDecodeState":
+        self.length = 0
+        return self
+
+
 class AutoRegressive(ViT):
     """``AutoRegressive(vocab_size, **vit_kwargs)`` (reference networks/vit.py:249-260): token ids -> vocabulary embedding -> the
-    ViT on the embedded tokens -> Linear head over the vocabulary (keys ``vocab_embed.weight``, ``head.{weight,bias}``)."""
+    ViT on the embedded tokens -> Linear head over the vocabulary (keys ``vocab_embed.weight``, ``head.{weight,bias}``).
+
+    ``decode_state`` / ``step`` run a causal decoder one token at a time on per-layer key / value caches: ``step`` costs one launch for
+    the embedded input, one per layer (``otvae_ar_layer_step``) and one for the head, and returns the logits the full forward pass
+    produces at that position."""
 
     def __init__(self, vocab_size: int, **vit_kwargs):
         super().__init__(**vit_kwargs)
@@ -411,3 +432,46 @@ class AutoRegressive(ViT):
 
     def forward(self, x: Tensor, labels: Optional[Tensor] = None, time: Optional[Tensor] = None) -> Tensor:
         return self.head(super().forward(self.vocab_embed(x), labels, time))
+
+    def decode_state(self, batch_size: int, max_tokens: Optional[int] = None) -> ARDecodeState:
+        """A fresh ``ARDecodeState`` for ``batch_size`` sequences of up to ``max_tokens`` (default: all input positions) tokens.
+        Eligibility is decided here, once: ``NotImplementedError`` (with the reason) unless the decoder is causal, has no
+        cross-attention stage (``preprocess_depth is None``), reads its output from exactly the input tokens, and drops nothing
+        (eval mode, or every dropout 0)."""
+        n_input = self.n_tokens["input"]
+        if not self.causal_mask:
+            raise NotImplementedError("cached decoding needs `causal_mask=True`: without the mask every token attends to later ones")
+        if self.prepocess is not None or not isinstance(self.transformer, _Encoder):
+            raise NotImplementedError("cached decoding is not implemented for the cross-attention decoder (`preprocess_depth`)")
+        if self.output_tokens_indices != self.token_indices["input"]:
+            raise NotImplementedError("cached decoding needs `output_tokens` to select exactly the input tokens")
+        if self.training and max(self.attn_dropout, self.positional_embed.p) > 0:
+            raise NotImplementedError("cached decoding has no dropout: call `.eval()` first or construct the decoder with dropout 0")
+        max_tokens = n_input if max_tokens is None else int(max_tokens)
+        if batch_size < 1 or not 1 <= max_tokens <= n_input:
+            raise ValueError(f"`batch_size` must be positive and `max_tokens` within 1 .. {n_input} (the decoder's input positions), "
+                             f"got {batch_size} / {max_tokens}")
+        heads = self.transformer.layers[0].self_attn.num_heads
+        return ARDecodeState(batch_size, max_tokens, len(self.transformer.layers), heads, self.dim // heads, self.vocab_embed.weight.device)
+
+    @torch.no_grad()
+    def step(self, ids_col: Tensor, state: ARDecodeState) -> Tensor:
+        """Advances every row by the token ``ids_col`` (int64 [B]) at position ``state.length`` and returns the logits [B, K] of that
+        position: ``self(ids)[:, state.length]`` for any ``ids`` that agree with the tokens consumed so far.
+
+        Embed and class tokens sit AFTER the input tokens in the ViT's token order, so under the causal mask no input token attends
+        to them: the step route does not compute them (and needs no ``labels``), and its logits still equal the full forward's."""
+        if state.length >= state.max_tokens:
+            raise ValueError(f"the decode state holds {state.max_tokens} tokens and all of them have been consumed")
+        if ids_col.dim() != 1 or ids_col.shape[0] != state.batch_size:
+            raise ValueError(f"`ids_col` must be [{state.batch_size}], got {list(ids_col.shape)}")
+        pos, pe = state.length, self.positional_embed
+        x = HF.ar_embed_step(ids_col, pos, self.vocab_embed.weight, pe.position_embeddings.weight, pe.LayerNorm.weight, pe.LayerNorm.bias,
+                             pe.LayerNorm.eps)
+        for layer, kc, vc in zip(self.transformer.layers, state.kcache, state.vcache):
+            at = layer.self_attn
+            x = HF.ar_layer_step(x, pos, at.num_heads, at.in_proj_weight, at.in_proj_bias, at.out_proj.weight, at.out_proj.bias,
+                                 layer.norm1.weight, layer.norm1.bias, layer.norm1.eps, layer.linear1.weight, layer.linear1.bias,
+                                 layer.linear2.weight, layer.linear2.bias, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, kc, vc)
+        state.length = pos + 1
+        return self.head(x.unsqueeze(1)).squeeze(1)
