@@ -319,40 +319,21 @@ int otvae_layernorm_dropout_bwd(const float* xs, const float* gy, const float* g
                                 float* dbeta, float* ws, void* stream);
 int otvae_layernorm_dropout_mask(int M, int D, float p, const int64_t* used, uint8_t* keep, void* stream);
 
-/* ---- GaussianPrior (prior/gaussian.py:63-96) + Prior.forward scaling (prior/base.py:74-78) ---------------- */
-/* h [B][S][2D] (S = H*W positions, channels-last) ; eps,z [B][S][D]; loss[B] = coeff * KL(q||N(0,I)) */
-int otvae_gaussian_prior_fwd(const float* h, const float* eps, int B, int S, int D, float coeff,
-                             float* z, float* loss, void* stream);
-int otvae_gaussian_prior_bwd(const float* h, const float* eps, const float* gz, const float* gloss,
-                             int B, int S, int D, float coeff, float* gh, void* stream);
-/* the options of GaussianPrior (prior/gaussian.py:38-41,63-96; prior/base.py:65-68).  mode bit 0: empirical_kl -- the
- * Monte-Carlo estimate sum log q(z) - log p(z) at the drawn z instead of the closed form; bit 1: fixed_var -- q = N(h, s) with
- * s = 1, or temp[b] + 1e-8 when a per-sample temperature temp[B] is given (`time` of encode); h is then [B][S][D] (no
- * log-variance half).  mode 0 = otvae_gaussian_prior_fwd / _bwd. */
-int otvae_gaussian_prior_ex_fwd(const float* h, const float* eps, const float* temp, int B, int S, int D, float coeff, int mode,
-                                float* z, float* loss, void* stream);
-int otvae_gaussian_prior_ex_bwd(const float* h, const float* eps, const float* temp, const float* gz, const float* gloss, int B,
-                                int S, int D, float coeff, int mode, float* gh, void* stream);
-
-/* ---- ConditionalGaussianPrior (prior/conditional_gaussian.py:84-93): the same re-parametrisation against a per-sample
- * diagonal prior N(prior_mean, exp(prior_log_std)^2) (rows of the class embeddings gathered by label).  h [B][2n]
- * (mu | log_var), eps, z, prior_mean, prior_log_std [B][n]; loss[B] = coeff * KL(q || p).  Backward also returns the
- * gradients of the gathered prior rows (nullable). */
-int otvae_gaussian_prior_cond_fwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std, int B,
-                                  int n, float coeff, float* z, float* loss, void* stream);
-int otvae_gaussian_prior_cond_bwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std,
-                                  const float* gz, const float* gloss, int B, int n, float coeff, float* gh,
-                                  float* g_prior_mean, float* g_prior_log_std, void* stream);
-
-/* The same with the options ConditionalGaussianPrior inherits from GaussianPrior (prior/conditional_gaussian.py:44-50 over
- * prior/gaussian.py:58-96, prior/base.py:65-68): mode bit 0 = empirical_kl (log q(z) - log p_y(z)), bit 1 = fixed_var (unit variance, h
- * holds the means only), and a re-parametrisation dimension other than 1: h [B][S][2 D] ([B][S][D] with fixed_var) = torch.chunk on a
- * dimension with S entries in front of it; eps, z and the gathered prior rows [B][S * D]. */
-int otvae_gaussian_prior_cond_ex_fwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std, int B, int S,
-                                     int D, float coeff, int mode, float* z, float* loss, void* stream);
-int otvae_gaussian_prior_cond_ex_bwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std,
-                                     const float* gz, const float* gloss, int B, int S, int D, float coeff, int mode, float* gh,
-                                     float* g_prior_mean, float* g_prior_log_std, void* stream);
+/* ---- GaussianPrior / ConditionalGaussianPrior (prior/gaussian.py:58-96, prior/conditional_gaussian.py:44-93) + Prior.forward
+ * scaling (prior/base.py:74-78): re-parametrisation z = mu + eps sd and loss[B] = coeff * KL(q || p) in one pass, explicit backward.
+ * h [B][S][2D]: within each of the S slices the first D entries are the means, the next D the log-variances (channels-last maps:
+ * S = H*W positions; torch.chunk on another dimension: S = the sizes in front of it); eps, z [B][S*D].
+ * prior_mean, prior_log_std [B][S*D] (rows of the class embeddings gathered by label): p = N(prior_mean, exp(prior_log_std)^2) per
+ * sample; both NULL: p = N(0, I).  The backward also returns the gradients of the gathered rows (each nullable).
+ * mode bit 0: empirical_kl -- the Monte-Carlo estimate sum log q(z) - log p(z) at the drawn z instead of the closed form;
+ * bit 1: fixed_var -- q = N(h, s) with s = 1, or temp[b] + 1e-8 when a per-sample temperature temp[B] is given (`time` of encode;
+ * NULL otherwise, and never with a conditional prior); h is then [B][S][D] (no log-variance half).  gz, gloss: nullable. */
+int otvae_gaussian_prior_fwd(const float* h, const float* eps, const float* temp, const float* prior_mean,
+                             const float* prior_log_std, int B, int S, int D, float coeff, int mode, float* z, float* loss,
+                             void* stream);
+int otvae_gaussian_prior_bwd(const float* h, const float* eps, const float* temp, const float* prior_mean,
+                             const float* prior_log_std, const float* gz, const float* gloss, int B, int S, int D, float coeff,
+                             int mode, float* gh, float* g_prior_mean, float* g_prior_log_std, void* stream);
 
 /* ---- VAE.nelbo reduction (model/vae.py:158-176) ----------------------------------------------------------- */
 /* out[3] = {total, recon, prior}: recon = mean((pred-target)^2) over numel entries, prior = mean(prior_loss[0..B))/chw.

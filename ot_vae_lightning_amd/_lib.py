@@ -103,14 +103,8 @@ SIGNATURES = {
     "otvae_layernorm_dropout_mask": (i32, [i32, i32, f32, vp, vp, vp]),
     "otvae_dropout_fwd": (i32, [vp, i64, i32, i32, f32, vp, i32, vp, vp, vp]),
     "otvae_dropout_bwd": (i32, [vp, vp, i64, i32, i32, f32, vp, vp, vp]),
-    "otvae_gaussian_prior_fwd": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, vp]),
-    "otvae_gaussian_prior_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, vp, vp]),
-    "otvae_gaussian_prior_ex_fwd": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp]),
-    "otvae_gaussian_prior_ex_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
-    "otvae_gaussian_prior_cond_fwd": (i32, [vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]),
-    "otvae_gaussian_prior_cond_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]),
-    "otvae_gaussian_prior_cond_ex_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp]),
-    "otvae_gaussian_prior_cond_ex_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
+    "otvae_gaussian_prior_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp]),
+    "otvae_gaussian_prior_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
     "otvae_copy_batched": (i32, [i32, vp, vp, vp, vp]),
     "otvae_nelbo_ws": (i32, []),
     "otvae_nelbo_fwd": (i32, [vp, vp, i64, vp, i32, f32, vp, vp, vp]),

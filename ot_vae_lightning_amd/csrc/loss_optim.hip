@@ -1,26 +1,81 @@
 // GaussianPrior re-parametrisation + closed-form KL (reference prior/gaussian.py:63-96, prior/base.py:74-78),
 // the nelbo reduction of VAE.nelbo (model/vae.py:158-176) and the Adam update configured by
 // VAE.configure_optimizers (model/vae.py:148-151), each fused into one pass over its data.
+#include <type_traits>
+
 #include "common.h"
 
-// ---- GaussianPrior ------------------------------------------------------------------------------------------
-// h [B][S][2D]: mu = h[..., :D], log_var = h[..., D:]; one workgroup per sample.
+// ---- GaussianPrior / ConditionalGaussianPrior (prior/gaussian.py:58-96, prior/conditional_gaussian.py:44-93, prior/base.py:65-68) ----
+// One workgroup per sample.  h is [B][S][2 D]: within each of the S slices the first D entries are the means, the next D the
+// log-variances (torch.chunk on dimension r of a contiguous tensor: S = the sizes in front of r, D = half of r's size times the sizes
+// behind it; channels-last maps: S = H W positions).  eps / z and the prior rows pm / pl (class embeddings gathered by label) are
+// [B][S * D].  The options are compile-time:
+//   COND   p = N(pm, exp(pl)^2) per sample instead of N(0, I)
+//   EMP    empirical_kl: the Monte-Carlo estimate log q(z) - log p(z) at the drawn z instead of the closed form
+//   FIXED  fixed_var: q = N(h, s), s = 1 or the per-sample temperature + 1e-8; h carries no log-variance half: [B][S][D]
+// With z = mu + eps sd, lsd = log sd, l = pl, ip = exp(-2 l), and (mp, l, ip) = (0, 0, 1) without a conditional prior:
+//   closed form   KL = l - lsd + (sd^2 + (mu - mp)^2) ip / 2 - 1/2          empirical   KL = ((z - mp)^2 ip - eps^2) / 2 - lsd + l
+struct PriorElem {
+    size_t at;                 // of mu in this sample's h (and of its gradient); log_var sits D further on
+    float mu, lsd, sd, e, z;   // q's mean, log standard deviation and standard deviation, the draw, the re-parametrised sample
+    float mp, l, ip;           // p's mean, log standard deviation and 1 / variance
+};
+
+template <bool COND, bool FIXED>
+__device__ __forceinline__ PriorElem prior_elem(const float* __restrict__ hb, const float* __restrict__ eps, const float* __restrict__ pm,
+                                                const float* __restrict__ pl, float sfix, int D, size_t row, int i) {
+    PriorElem q;
+    if constexpr (FIXED) {
+        q.at = i;
+        q.lsd = logf(sfix);
+        q.sd = sfix;
+    } else {
+        const int s = i / D, d = i - s * D;
+        q.at = (size_t)s * 2 * D + d;
+        q.lsd = 0.5f * hb[q.at + D];
+        q.sd = __expf(q.lsd);
+    }
+    q.mu = hb[q.at];
+    q.e = eps[row + i];
+    q.z = fmaf(q.e, q.sd, q.mu);
+    q.mp = COND ? pm[row + i] : 0.f;
+    q.l = COND ? pl[row + i] : 0.f;
+    q.ip = COND ? __expf(-2.f * q.l) : 1.f;
+    return q;
+}
+
+// fixed_var's standard deviation: no temperature goes with a conditional prior
+template <bool COND>
+__device__ __forceinline__ float prior_sfix(const float* __restrict__ temp, int b) {
+    return !COND && temp ? temp[b] + 1e-8f : 1.f;
+}
+
+template <bool COND, bool EMP, bool FIXED>
 __global__ __launch_bounds__(256) void gaussian_prior_fwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                 int S, int D, float coeff, float* __restrict__ z,
-                                                                 float* __restrict__ loss) {
+                                                                 const float* __restrict__ temp, const float* __restrict__ pm,
+                                                                 const float* __restrict__ pl, int S, int D, float coeff,
+                                                                 float* __restrict__ z, float* __restrict__ loss) {
     __shared__ float red[4];
-    const int b = blockIdx.x;
-    const int n = S * D;
-    const float* hb = h + (size_t)b * S * 2 * D;
+    const int b = blockIdx.x, n = S * D;
+    const size_t row = (size_t)b * n;
+    const float* hb = h + (size_t)b * S * (FIXED ? D : 2 * D);
+    const float sfix = prior_sfix<COND>(temp, b);
     float kl = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) {
-        const int s = i / D, d = i - s * D;
-        const float mu = hb[(size_t)s * 2 * D + d];
-        const float lv = hb[(size_t)s * 2 * D + D + d];
-        const float sd = __expf(0.5f * lv);
-        const float var = sd * sd;
-        z[(size_t)b * n + i] = fmaf(eps[(size_t)b * n + i], sd, mu);
-        kl += 0.5f * (mu * mu - __logf(var) + var - 1.f);
+        const PriorElem q = prior_elem<COND, FIXED>(hb, eps, pm, pl, sfix, D, row, i);
+        z[row + i] = q.z;
+        if constexpr (EMP) {
+            const float dz = q.z - q.mp;
+            kl += 0.5f * (dz * dz * q.ip - q.e * q.e) - q.lsd + q.l;
+        } else if constexpr (COND) {
+            const float dm = q.mu - q.mp;
+            kl += q.l - q.lsd + 0.5f * (q.sd * q.sd + dm * dm) * q.ip - 0.5f;
+        } else if constexpr (FIXED) {   // p = N(0, I): the closed form without the factors that are 1
+            kl += 0.5f * (q.mu * q.mu + q.sd * q.sd - 1.f) - q.lsd;
+        } else {   // the route every default training step takes: its rounding is pinned bit for bit (bench.py --dump-outputs)
+            const float var = q.sd * q.sd;
+            kl += 0.5f * (q.mu * q.mu - __logf(var) + var - 1.f);
+        }
     }
     kl = wave_sum(kl);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = kl;
@@ -28,292 +83,80 @@ __global__ __launch_bounds__(256) void gaussian_prior_fwd_kernel(const float* __
     if (threadIdx.x == 0) loss[b] = coeff * ((red[0] + red[1]) + (red[2] + red[3]));
 }
 
+// KL depends on the means through dd^2 ip / 2, dd = mu - mp (empirical: z - mp, which also carries log_var: d z / d lv = eps sd / 2):
+//   d KL / d mu = dd ip = -d KL / d mp        2 d KL / d lv = sd^2 ip - 1   (empirical: dd ip eps sd - 1)
+//   d KL / d l  = 1 - (sd^2 + dd^2) ip        (empirical: 1 - dd^2 ip)
+template <bool COND, bool EMP, bool FIXED>
 __global__ __launch_bounds__(256) void gaussian_prior_bwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                 const float* __restrict__ gz, const float* __restrict__ gloss,
-                                                                 int S, int D, float coeff, float* __restrict__ gh) {
-    const int b = blockIdx.x;
-    const int n = S * D;
-    const float* hb = h + (size_t)b * S * 2 * D;
-    float* gb = gh + (size_t)b * S * 2 * D;
+                                                                 const float* __restrict__ temp, const float* __restrict__ pm,
+                                                                 const float* __restrict__ pl, const float* __restrict__ gz,
+                                                                 const float* __restrict__ gloss, int S, int D, float coeff,
+                                                                 float* __restrict__ gh, float* __restrict__ gpm,
+                                                                 float* __restrict__ gpl) {
+    const int b = blockIdx.x, n = S * D;
+    const size_t row = (size_t)b * n, hrow = (size_t)b * S * (FIXED ? D : 2 * D);
+    const float* hb = h + hrow;
+    float* gb = gh + hrow;
+    const float sfix = prior_sfix<COND>(temp, b);
     const float gl = (gloss ? gloss[b] : 0.f) * coeff;
     for (int i = threadIdx.x; i < n; i += 256) {
-        const int s = i / D, d = i - s * D;
-        const float mu = hb[(size_t)s * 2 * D + d];
-        const float lv = hb[(size_t)s * 2 * D + D + d];
-        const float sd = __expf(0.5f * lv);
-        const float g = gz ? gz[(size_t)b * n + i] : 0.f;
-        gb[(size_t)s * 2 * D + d] = fmaf(gl, mu, g);
-        // d z/d lv = eps*sd/2 ; d KL/d lv = (var - 1)/2
-        gb[(size_t)s * 2 * D + D + d] = 0.5f * (g * eps[(size_t)b * n + i] * sd + gl * (sd * sd - 1.f));
+        const PriorElem q = prior_elem<COND, FIXED>(hb, eps, pm, pl, sfix, D, row, i);
+        const float g = gz ? gz[row + i] : 0.f;
+        const float dd = (EMP ? q.z : q.mu) - q.mp;
+        gb[q.at] = fmaf(gl, dd * q.ip, g);
+        if constexpr (!FIXED) {
+            const float dlv2 = EMP ? dd * q.ip * q.e * q.sd - 1.f : q.sd * q.sd * q.ip - 1.f;
+            gb[q.at + D] = 0.5f * (g * q.e * q.sd + gl * dlv2);
+        }
+        if constexpr (COND) {
+            if (gpm) gpm[row + i] = -gl * dd * q.ip;
+            if (gpl) gpl[row + i] = gl * (1.f - (EMP ? dd * dd : q.sd * q.sd + dd * dd) * q.ip);
+        }
     }
 }
 
-extern "C" int otvae_gaussian_prior_fwd(const float* h, const float* eps, int B, int S, int D, float coeff, float* z,
-                                        float* loss, void* stream) {
-    OTVAE_REQUIRE(h && eps && z && loss && B > 0 && S > 0 && D > 0, "otvae_gaussian_prior_fwd: bad argument");
-    gaussian_prior_fwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, S, D, coeff, z, loss);
+// what both entry points require of their shared arguments; the instantiation is picked by (a conditional prior is given, mode)
+static int gaussian_prior_args(const char* who, const float* h, const float* eps, const float* temp, const float* prior_mean,
+                               const float* prior_log_std, int B, int S, int D, int mode) {
+    OTVAE_REQUIRE(h && eps && B > 0 && S > 0 && D > 0 && mode >= 0 && mode <= 3, "%s: bad argument", who);
+    OTVAE_REQUIRE((prior_mean != nullptr) == (prior_log_std != nullptr), "%s: prior_mean and prior_log_std come together", who);
+    OTVAE_REQUIRE(!temp || (mode & 2), "%s: a temperature goes with fixed_var (mode bit 1)", who);
+    OTVAE_REQUIRE(!temp || !prior_mean, "%s: no temperature with a conditional prior", who);
+    return OTVAE_OK;
+}
+
+// launch(COND, EMP, FIXED as std::bool_constant values)
+template <class Launch>
+static void gaussian_prior_dispatch(bool cond, int mode, Launch&& launch) {
+    auto pick = [&](bool v, auto&& next) { v ? next(std::true_type{}) : next(std::false_type{}); };
+    pick(cond, [&](auto c) { pick(mode & 1, [&](auto e) { pick(mode & 2, [&](auto f) { launch(c, e, f); }); }); });
+}
+
+extern "C" int otvae_gaussian_prior_fwd(const float* h, const float* eps, const float* temp, const float* prior_mean,
+                                        const float* prior_log_std, int B, int S, int D, float coeff, int mode, float* z, float* loss,
+                                        void* stream) {
+    const int rc = gaussian_prior_args("otvae_gaussian_prior_fwd", h, eps, temp, prior_mean, prior_log_std, B, S, D, mode);
+    if (rc != OTVAE_OK) return rc;
+    OTVAE_REQUIRE(z && loss, "otvae_gaussian_prior_fwd: NULL output");
+    gaussian_prior_dispatch(prior_mean != nullptr, mode, [&](auto c, auto e, auto f) {
+        gaussian_prior_fwd_kernel<c(), e(), f()><<<B, 256, 0, (hipStream_t)stream>>>(h, eps, temp, prior_mean, prior_log_std, S, D, coeff,
+                                                                                     z, loss);
+    });
     OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_fwd");
     return OTVAE_OK;
 }
 
-extern "C" int otvae_gaussian_prior_bwd(const float* h, const float* eps, const float* gz, const float* gloss, int B, int S,
-                                        int D, float coeff, float* gh, void* stream) {
-    OTVAE_REQUIRE(h && eps && gh && B > 0 && S > 0 && D > 0, "otvae_gaussian_prior_bwd: bad argument");
-    gaussian_prior_bwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, gz, gloss, S, D, coeff, gh);
+extern "C" int otvae_gaussian_prior_bwd(const float* h, const float* eps, const float* temp, const float* prior_mean,
+                                        const float* prior_log_std, const float* gz, const float* gloss, int B, int S, int D,
+                                        float coeff, int mode, float* gh, float* g_prior_mean, float* g_prior_log_std, void* stream) {
+    const int rc = gaussian_prior_args("otvae_gaussian_prior_bwd", h, eps, temp, prior_mean, prior_log_std, B, S, D, mode);
+    if (rc != OTVAE_OK) return rc;
+    OTVAE_REQUIRE(gh, "otvae_gaussian_prior_bwd: NULL output");
+    gaussian_prior_dispatch(prior_mean != nullptr, mode, [&](auto c, auto e, auto f) {
+        gaussian_prior_bwd_kernel<c(), e(), f()><<<B, 256, 0, (hipStream_t)stream>>>(h, eps, temp, prior_mean, prior_log_std, gz, gloss, S,
+                                                                                     D, coeff, gh, g_prior_mean, g_prior_log_std);
+    });
     OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_bwd");
-    return OTVAE_OK;
-}
-
-// ---- GaussianPrior options (prior/gaussian.py:63-96, prior/base.py:65-68): mode bit 0 = empirical_kl (the Monte-Carlo estimate
-// sum log q(z) - log p(z) at the drawn z instead of the closed form), bit 1 = fixed_var (q = N(h, s), s = 1 or the per-sample
-// temperature + 1e-8; h carries no log-variance half: [B][S][D]).
-//   closed form:  0.5 (mu^2 - log s^2 + s^2 - 1)            empirical:  0.5 z^2 - 0.5 eps^2 - log s,   z = mu + s eps
-__global__ __launch_bounds__(256) void gaussian_prior_ex_fwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                    const float* __restrict__ temp, int S, int D, float coeff, int mode,
-                                                                    float* __restrict__ z, float* __restrict__ loss) {
-    __shared__ float red[4];
-    const int b = blockIdx.x;
-    const int n = S * D;
-    const bool emp = mode & 1, fixed = mode & 2;
-    const float* hb = h + (size_t)b * S * (fixed ? D : 2 * D);
-    const float sfix = temp ? temp[b] + 1e-8f : 1.f;
-    float kl = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int s = i / D, d = i - s * D;
-        float mu, sd, lsd;  // mean, standard deviation, its logarithm
-        if (fixed) {
-            mu = hb[i];
-            sd = sfix;
-            lsd = logf(sfix);
-        } else {
-            mu = hb[(size_t)s * 2 * D + d];
-            lsd = 0.5f * hb[(size_t)s * 2 * D + D + d];
-            sd = __expf(lsd);
-        }
-        const float e = eps[(size_t)b * n + i];
-        const float zz = fmaf(e, sd, mu);
-        z[(size_t)b * n + i] = zz;
-        kl += emp ? 0.5f * (zz * zz - e * e) - lsd : 0.5f * (mu * mu + sd * sd - 1.f) - lsd;
-    }
-    kl = wave_sum(kl);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = kl;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[b] = coeff * ((red[0] + red[1]) + (red[2] + red[3]));
-}
-
-__global__ __launch_bounds__(256) void gaussian_prior_ex_bwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                    const float* __restrict__ temp, const float* __restrict__ gz,
-                                                                    const float* __restrict__ gloss, int S, int D, float coeff,
-                                                                    int mode, float* __restrict__ gh) {
-    const int b = blockIdx.x;
-    const int n = S * D;
-    const bool emp = mode & 1, fixed = mode & 2;
-    const size_t row = (size_t)S * (fixed ? D : 2 * D);
-    const float* hb = h + (size_t)b * row;
-    float* gb = gh + (size_t)b * row;
-    const float sfix = temp ? temp[b] + 1e-8f : 1.f;
-    const float gl = (gloss ? gloss[b] : 0.f) * coeff;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int s = i / D, d = i - s * D;
-        const float e = eps[(size_t)b * n + i];
-        const float g = gz ? gz[(size_t)b * n + i] : 0.f;
-        if (fixed) {
-            const float mu = hb[i];
-            gb[i] = fmaf(gl, emp ? fmaf(e, sfix, mu) : mu, g);
-        } else {
-            const float mu = hb[(size_t)s * 2 * D + d];
-            const float sd = __expf(0.5f * hb[(size_t)s * 2 * D + D + d]);
-            const float zz = fmaf(e, sd, mu);
-            // d z / d lv = eps sd / 2;  closed form: d KL / d mu = mu, d KL / d lv = (sd^2 - 1) / 2
-            // empirical: d L / d mu = z,  d L / d lv = z eps sd / 2 - 1/2
-            gb[(size_t)s * 2 * D + d] = fmaf(gl, emp ? zz : mu, g);
-            gb[(size_t)s * 2 * D + D + d] = 0.5f * (g * e * sd + gl * (emp ? zz * e * sd - 1.f : sd * sd - 1.f));
-        }
-    }
-}
-
-extern "C" int otvae_gaussian_prior_ex_fwd(const float* h, const float* eps, const float* temp, int B, int S, int D, float coeff,
-                                           int mode, float* z, float* loss, void* stream) {
-    OTVAE_REQUIRE(h && eps && z && loss && B > 0 && S > 0 && D > 0 && mode >= 0 && mode <= 3, "otvae_gaussian_prior_ex_fwd: bad argument");
-    OTVAE_REQUIRE(!temp || (mode & 2), "otvae_gaussian_prior_ex_fwd: a temperature goes with fixed_var (mode bit 1)");
-    gaussian_prior_ex_fwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, temp, S, D, coeff, mode, z, loss);
-    OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_ex_fwd");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_gaussian_prior_ex_bwd(const float* h, const float* eps, const float* temp, const float* gz, const float* gloss,
-                                           int B, int S, int D, float coeff, int mode, float* gh, void* stream) {
-    OTVAE_REQUIRE(h && eps && gh && B > 0 && S > 0 && D > 0 && mode >= 0 && mode <= 3, "otvae_gaussian_prior_ex_bwd: bad argument");
-    OTVAE_REQUIRE(!temp || (mode & 2), "otvae_gaussian_prior_ex_bwd: a temperature goes with fixed_var (mode bit 1)");
-    gaussian_prior_ex_bwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, temp, gz, gloss, S, D, coeff, mode, gh);
-    OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_ex_bwd");
-    return OTVAE_OK;
-}
-
-// ---- ConditionalGaussianPrior (prior/conditional_gaussian.py:84-93): KL(q || p_y) against a per-sample diagonal prior ----
-// h [B][2n] (mu | log_var), eps / z [B][n], prior mean pm and log standard deviation pl [B][n] (rows gathered by label):
-//   KL = sum_i  pl_i - lv_i/2 + (exp(lv_i) + (mu_i - pm_i)^2) / (2 exp(2 pl_i)) - 1/2
-__global__ __launch_bounds__(256) void gaussian_prior_cond_fwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                      const float* __restrict__ pm, const float* __restrict__ pl,
-                                                                      int n, float coeff, float* __restrict__ z,
-                                                                      float* __restrict__ loss) {
-    __shared__ float red[4];
-    const int b = blockIdx.x;
-    const float* hb = h + (size_t)b * 2 * n;
-    float kl = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float mu = hb[i], lv = hb[n + i];
-        const float sd = __expf(0.5f * lv), var = sd * sd;
-        const float dm = mu - pm[(size_t)b * n + i], l = pl[(size_t)b * n + i];
-        z[(size_t)b * n + i] = fmaf(eps[(size_t)b * n + i], sd, mu);
-        kl += l - 0.5f * lv + 0.5f * (var + dm * dm) * __expf(-2.f * l) - 0.5f;
-    }
-    kl = wave_sum(kl);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = kl;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[b] = coeff * ((red[0] + red[1]) + (red[2] + red[3]));
-}
-
-__global__ __launch_bounds__(256) void gaussian_prior_cond_bwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                      const float* __restrict__ pm, const float* __restrict__ pl,
-                                                                      const float* __restrict__ gz, const float* __restrict__ gloss,
-                                                                      int n, float coeff, float* __restrict__ gh,
-                                                                      float* __restrict__ gpm, float* __restrict__ gpl) {
-    const int b = blockIdx.x;
-    const float* hb = h + (size_t)b * 2 * n;
-    float* gb = gh + (size_t)b * 2 * n;
-    const float gl = (gloss ? gloss[b] : 0.f) * coeff;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float mu = hb[i], lv = hb[n + i];
-        const float sd = __expf(0.5f * lv), var = sd * sd;
-        const float dm = mu - pm[(size_t)b * n + i], l = pl[(size_t)b * n + i];
-        const float ip = __expf(-2.f * l);  // 1 / sigma_p^2
-        const float g = gz ? gz[(size_t)b * n + i] : 0.f;
-        gb[i] = fmaf(gl, dm * ip, g);
-        gb[n + i] = 0.5f * (g * eps[(size_t)b * n + i] * sd + gl * (var * ip - 1.f));
-        if (gpm) gpm[(size_t)b * n + i] = -gl * dm * ip;
-        if (gpl) gpl[(size_t)b * n + i] = gl * (1.f - (var + dm * dm) * ip);
-    }
-}
-
-extern "C" int otvae_gaussian_prior_cond_fwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std,
-                                             int B, int n, float coeff, float* z, float* loss, void* stream) {
-    OTVAE_REQUIRE(h && eps && prior_mean && prior_log_std && z && loss && B > 0 && n > 0, "otvae_gaussian_prior_cond_fwd: bad argument");
-    gaussian_prior_cond_fwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, prior_mean, prior_log_std, n, coeff, z, loss);
-    OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_cond_fwd");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_gaussian_prior_cond_bwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std,
-                                             const float* gz, const float* gloss, int B, int n, float coeff, float* gh,
-                                             float* g_prior_mean, float* g_prior_log_std, void* stream) {
-    OTVAE_REQUIRE(h && eps && prior_mean && prior_log_std && gh && B > 0 && n > 0, "otvae_gaussian_prior_cond_bwd: bad argument");
-    gaussian_prior_cond_bwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, prior_mean, prior_log_std, gz, gloss, n, coeff, gh,
-                                                                       g_prior_mean, g_prior_log_std);
-    OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_cond_bwd");
-    return OTVAE_OK;
-}
-
-// ---- ConditionalGaussianPrior with the options it inherits (prior/conditional_gaussian.py:44-93 over prior/gaussian.py:58-96,
-// prior/base.py:65-68): empirical_kl (mode bit 0), fixed_var (bit 1) and a re-parametrisation dimension other than 1.  h is
-// [B][S][2 D] (fixed_var: [B][S][D]): within each of the S slices the first D entries are the means, the next D the log-variances
-// (torch.chunk on dimension r of a contiguous tensor: S = the sizes in front of r, D = half of r's size times the sizes behind it).
-// eps / z / pm / pl are [B][S * D].  With l = log sigma_p, ip = exp(-2 l), dm = mu - mu_p, lsd = log sigma_q (0 when fixed):
-//   closed form   KL = l - lsd + (sigma_q^2 + dm^2) ip / 2 - 1/2
-//   empirical     KL = log q(z) - log p(z) = ((z - mu_p)^2 ip - eps^2) / 2 - lsd + l,   z = mu + eps sigma_q
-__global__ __launch_bounds__(256) void gaussian_prior_cond_ex_fwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                         const float* __restrict__ pm, const float* __restrict__ pl,
-                                                                         int S, int D, float coeff, int mode, float* __restrict__ z,
-                                                                         float* __restrict__ loss) {
-    __shared__ float red[4];
-    const int b = blockIdx.x, n = S * D;
-    const bool emp = mode & 1, fixed = mode & 2;
-    const float* hb = h + (size_t)b * S * (fixed ? D : 2 * D);
-    float kl = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int s = i / D, d = i - s * D;
-        const float mu = fixed ? hb[i] : hb[(size_t)s * 2 * D + d];
-        const float lsd = fixed ? 0.f : 0.5f * hb[(size_t)s * 2 * D + D + d];
-        const float sd = fixed ? 1.f : __expf(lsd);
-        const float e = eps[(size_t)b * n + i];
-        const float zz = fmaf(e, sd, mu);
-        z[(size_t)b * n + i] = zz;
-        const float l = pl[(size_t)b * n + i], ip = __expf(-2.f * l), mp = pm[(size_t)b * n + i];
-        if (emp) {
-            const float dz = zz - mp;
-            kl += 0.5f * (dz * dz * ip - e * e) - lsd + l;
-        } else {
-            const float dm = mu - mp;
-            kl += l - lsd + 0.5f * (sd * sd + dm * dm) * ip - 0.5f;
-        }
-    }
-    kl = wave_sum(kl);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = kl;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[b] = coeff * ((red[0] + red[1]) + (red[2] + red[3]));
-}
-
-__global__ __launch_bounds__(256) void gaussian_prior_cond_ex_bwd_kernel(const float* __restrict__ h, const float* __restrict__ eps,
-                                                                         const float* __restrict__ pm, const float* __restrict__ pl,
-                                                                         const float* __restrict__ gz, const float* __restrict__ gloss,
-                                                                         int S, int D, float coeff, int mode, float* __restrict__ gh,
-                                                                         float* __restrict__ gpm, float* __restrict__ gpl) {
-    const int b = blockIdx.x, n = S * D;
-    const bool emp = mode & 1, fixed = mode & 2;
-    const size_t row = (size_t)S * (fixed ? D : 2 * D);
-    const float* hb = h + (size_t)b * row;
-    float* gb = gh + (size_t)b * row;
-    const float gl = (gloss ? gloss[b] : 0.f) * coeff;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int s = i / D, d = i - s * D;
-        const float mu = fixed ? hb[i] : hb[(size_t)s * 2 * D + d];
-        const float lsd = fixed ? 0.f : 0.5f * hb[(size_t)s * 2 * D + D + d];
-        const float sd = fixed ? 1.f : __expf(lsd);
-        const float e = eps[(size_t)b * n + i];
-        const float g = gz ? gz[(size_t)b * n + i] : 0.f;
-        const float l = pl[(size_t)b * n + i], ip = __expf(-2.f * l), mp = pm[(size_t)b * n + i];
-        float dmu, dlv, dmp, dl;   // d KL / d (mu, log_var, mu_p, l)
-        if (emp) {
-            const float dz = fmaf(e, sd, mu) - mp;
-            dmu = dz * ip;
-            dlv = 0.5f * (dz * ip * e * sd) - 0.5f;
-            dmp = -dz * ip;
-            dl = 1.f - dz * dz * ip;
-        } else {
-            const float dm = mu - mp;
-            dmu = dm * ip;
-            dlv = 0.5f * (sd * sd * ip - 1.f);
-            dmp = -dm * ip;
-            dl = 1.f - (sd * sd + dm * dm) * ip;
-        }
-        if (fixed) {
-            gb[i] = fmaf(gl, dmu, g);
-        } else {
-            gb[(size_t)s * 2 * D + d] = fmaf(gl, dmu, g);
-            gb[(size_t)s * 2 * D + D + d] = fmaf(gl, dlv, 0.5f * g * e * sd);
-        }
-        if (gpm) gpm[(size_t)b * n + i] = gl * dmp;
-        if (gpl) gpl[(size_t)b * n + i] = gl * dl;
-    }
-}
-
-extern "C" int otvae_gaussian_prior_cond_ex_fwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std,
-                                                int B, int S, int D, float coeff, int mode, float* z, float* loss, void* stream) {
-    OTVAE_REQUIRE(h && eps && prior_mean && prior_log_std && z && loss && B > 0 && S > 0 && D > 0 && mode >= 0 && mode <= 3,
-                  "otvae_gaussian_prior_cond_ex_fwd: bad argument");
-    gaussian_prior_cond_ex_fwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, prior_mean, prior_log_std, S, D, coeff, mode, z, loss);
-    OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_cond_ex_fwd");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_gaussian_prior_cond_ex_bwd(const float* h, const float* eps, const float* prior_mean, const float* prior_log_std,
-                                                const float* gz, const float* gloss, int B, int S, int D, float coeff, int mode,
-                                                float* gh, float* g_prior_mean, float* g_prior_log_std, void* stream) {
-    OTVAE_REQUIRE(h && eps && prior_mean && prior_log_std && gh && B > 0 && S > 0 && D > 0 && mode >= 0 && mode <= 3,
-                  "otvae_gaussian_prior_cond_ex_bwd: bad argument");
-    gaussian_prior_cond_ex_bwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(h, eps, prior_mean, prior_log_std, gz, gloss, S, D, coeff, mode,
-                                                                          gh, g_prior_mean, g_prior_log_std);
-    OTVAE_CHECK_LAUNCH("otvae_gaussian_prior_cond_ex_bwd");
     return OTVAE_OK;
 }
 

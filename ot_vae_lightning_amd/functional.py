@@ -1864,46 +1864,6 @@ def normal_like(like: Tensor, key: Tensor, stream_id: int = 0) -> Tensor:
     return normal_fill_(torch.empty(like.shape, device=like.device, dtype=torch.float32), key, stream_id)
 
 
-class _CondGaussianPriorFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, eps, pm, pl, coeff):
-        lib = _lib.load()
-        b, n = eps.shape
-        z = torch.empty_like(eps)
-        loss = torch.empty(b, device=h.device, dtype=torch.float32)
-        check(lib.otvae_gaussian_prior_cond_fwd(ptr(h), ptr(eps), ptr(pm), ptr(pl), b, n, float(coeff), ptr(z), ptr(loss),
-                                                stream()), "otvae_gaussian_prior_cond_fwd")
-        ctx.save_for_backward(h, eps, pm, pl)
-        ctx.coeff = float(coeff)
-        return z, loss
-
-    @staticmethod
-    def backward(ctx, gz, gloss):
-        lib = _lib.load()
-        h, eps, pm, pl = ctx.saved_tensors
-        b, n = eps.shape
-        gz = gz.contiguous() if gz is not None else None
-        gloss = gloss.contiguous() if gloss is not None else None
-        gh = torch.empty_like(h)
-        gpm = torch.empty_like(pm) if ctx.needs_input_grad[2] else None
-        gpl = torch.empty_like(pl) if ctx.needs_input_grad[3] else None
-        check(lib.otvae_gaussian_prior_cond_bwd(ptr(h), ptr(eps), ptr(pm), ptr(pl), ptr(gz), ptr(gloss), b, n, ctx.coeff, ptr(gh),
-                                                ptr(gpm), ptr(gpl), stream()), "otvae_gaussian_prior_cond_bwd")
-        return gh, None, gpm, gpl, None
-
-
-def gaussian_prior_conditional(h: Tensor, eps: Tensor, prior_mean: Tensor, prior_log_std: Tensor, coeff: float):
-    """(z, coeff * KL(q || N(prior_mean, exp(prior_log_std)^2))[B]) for h [B, 2, ...] re-parametrised on dim 1, everything
-    else flattened (reference prior/conditional_gaussian.py:84-93)."""
-    _lib.require_cuda(h, "prior input")
-    b = h.shape[0]
-    out_shape = list(h.shape)
-    out_shape[1] //= 2
-    flat = lambda t: t.reshape(b, -1).contiguous().float()  # noqa: E731
-    z, loss = _CondGaussianPriorFn.apply(flat(h), flat(eps), flat(prior_mean), flat(prior_log_std), coeff)
-    return z.reshape(out_shape), loss
-
-
 def gaussian_prior(h: Tensor, eps: Tensor, coeff: float) -> Tuple[Tensor, Tensor]:
     """(z, coeff*KL[B]) for the re-parametrised diagonal Gaussian (reference prior/gaussian.py:63-96)."""
     _lib.require_cuda(h, "prior input")
@@ -1919,36 +1879,37 @@ def gaussian_prior(h: Tensor, eps: Tensor, coeff: float) -> Tuple[Tensor, Tensor
     return torch.ops.otvae.gaussian_prior(as_nhwc(h), as_nhwc(eps), float(coeff))
 
 
-class _GaussianPriorExFn(torch.autograd.Function):
-    """``GaussianPrior`` with ``empirical_kl`` and / or ``fixed_var`` (and the temperature of ``encode(time=)``):
-    ``otvae_gaussian_prior_ex_fwd / _bwd`` on h flattened to [B, S = 1, D (or 2D)]."""
+class _GaussianPriorFn(torch.autograd.Function):
+    """``otvae_gaussian_prior_fwd / _bwd`` on flattened rows: h [B, S * 2D] (mode bit 1, fixed_var: [B, S * D]), eps and the prior
+    rows pm / pl [B, S * D], temp [B]; temp, pm and pl may be None."""
 
     @staticmethod
-    def forward(ctx, h, eps, temp, coeff, mode, s_):
-        lib = _lib.load()
-        b = h.shape[0]
-        d = (h.shape[1] if mode & 2 else h.shape[1] // 2) // s_
-        z = torch.empty((b, s_ * d), device=h.device, dtype=torch.float32)
+    def forward(ctx, h, eps, temp, pm, pl, coeff, mode, s_):
+        b, n = eps.shape
+        z = torch.empty_like(eps)
         loss = torch.empty(b, device=h.device, dtype=torch.float32)
-        check(lib.otvae_gaussian_prior_ex_fwd(ptr(h), ptr(eps), ptr(temp), b, s_, d, float(coeff), int(mode), ptr(z), ptr(loss), stream()),
-              "otvae_gaussian_prior_ex_fwd")
-        ctx.save_for_backward(h, eps, temp)
-        ctx.cfg = (float(coeff), int(mode), d, int(s_))
-        ctx.set_materialize_grads(False)
+        check(_lib.load().otvae_gaussian_prior_fwd(ptr(h), ptr(eps), ptr(temp), ptr(pm), ptr(pl), b, s_, n // s_, coeff, mode, ptr(z),
+                                                   ptr(loss), stream()), "otvae_gaussian_prior_fwd")
+        ctx.save_for_backward(h, eps, temp, pm, pl)
+        ctx.cfg = (coeff, mode, s_)
+        ctx.set_materialize_grads(False)  # gz / gloss are optional arguments of the backward kernel
         return z, loss
 
     @staticmethod
     def backward(ctx, gz, gloss):
         if gz is None and gloss is None:
-            return None, None, None, None, None, None
-        h, eps, temp = ctx.saved_tensors
-        coeff, mode, d, s_ = ctx.cfg
-        gh = torch.empty_like(h)
+            return (None,) * 8
+        h, eps, temp, pm, pl = ctx.saved_tensors
+        coeff, mode, s_ = ctx.cfg
+        b, n = eps.shape
         gz = gz.contiguous() if gz is not None else None
         gloss = gloss.contiguous() if gloss is not None else None
-        check(_lib.load().otvae_gaussian_prior_ex_bwd(ptr(h), ptr(eps), ptr(temp), ptr(gz), ptr(gloss), h.shape[0], s_, d, coeff, mode,
-                                                      ptr(gh), stream()), "otvae_gaussian_prior_ex_bwd")
-        return gh, None, None, None, None, None
+        gh = torch.empty_like(h)
+        gpm = torch.empty_like(pm) if ctx.needs_input_grad[3] else None
+        gpl = torch.empty_like(pl) if ctx.needs_input_grad[4] else None
+        check(_lib.load().otvae_gaussian_prior_bwd(ptr(h), ptr(eps), ptr(temp), ptr(pm), ptr(pl), ptr(gz), ptr(gloss), b, s_, n // s_,
+                                                   coeff, mode, ptr(gh), ptr(gpm), ptr(gpl), stream()), "otvae_gaussian_prior_bwd")
+        return gh, None, None, gpm, gpl, None, None, None
 
 
 def _reparam_layout(h: Tensor, reparam_dim: int, fixed_var: bool):
@@ -1970,68 +1931,23 @@ def _reparam_layout(h: Tensor, reparam_dim: int, fixed_var: bool):
     return s_, out_shape
 
 
-def gaussian_prior_ex(h: Tensor, eps: Tensor, coeff: float, empirical_kl: bool = False, fixed_var: bool = False,
-                      temperature: Optional[Tensor] = None, reparam_dim: int = 1) -> Tuple[Tensor, Tensor]:
+def gaussian_prior_general(h: Tensor, eps: Tensor, coeff: float, *, prior_mean: Optional[Tensor] = None,
+                           prior_log_std: Optional[Tensor] = None, empirical_kl: bool = False, fixed_var: bool = False,
+                           temperature: Optional[Tensor] = None, reparam_dim: int = 1) -> Tuple[Tensor, Tensor]:
     """(z, coeff * loss[B]) of ``GaussianPrior(empirical_kl=, fixed_var=, reparam_dim=)`` (reference prior/gaussian.py:63-96,
-    prior/base.py:65-68) for h re-parametrised on ``reparam_dim`` (fixed_var: z = h + s eps with s = 1 or temperature[b] + 1e-8)."""
+    prior/base.py:65-68) for h re-parametrised on ``reparam_dim`` (fixed_var: z = h + s eps with s = 1 or temperature[b] + 1e-8), and of
+    ``ConditionalGaussianPrior`` (prior/conditional_gaussian.py:84-93) when the prior rows [B, prod(dim)], laid out like z, are given."""
     _lib.require_cuda(h, "prior input")
     b = h.shape[0]
     s_, out_shape = _reparam_layout(h, reparam_dim, fixed_var)
-    flat = h.contiguous().reshape(b, -1)
-    temp = None
-    if temperature is not None:
-        if not fixed_var:
-            raise ValueError("a temperature (`time`) is only meaningful with fixed_var=True")
-        temp = temperature.reshape(b).float().contiguous()
+    if temperature is not None and not fixed_var:
+        raise ValueError("a temperature (`time`) is only meaningful with fixed_var=True")
+    if (prior_mean is None) != (prior_log_std is None):
+        raise ValueError("`prior_mean` and `prior_log_std` come together")
+    flat = lambda t: None if t is None else t.contiguous().reshape(b, -1).float()  # noqa: E731
+    temp = None if temperature is None else temperature.reshape(b).float().contiguous()
     mode = (1 if empirical_kl else 0) | (2 if fixed_var else 0)
-    z, loss = _GaussianPriorExFn.apply(flat.float(), eps.reshape(b, -1).float().contiguous(), temp, float(coeff), mode, s_)
-    return z.reshape(out_shape), loss
-
-
-class _CondGaussianPriorExFn(torch.autograd.Function):
-    """``ConditionalGaussianPrior`` with empirical_kl / fixed_var / a re-parametrisation dimension other than 1:
-    ``otvae_gaussian_prior_cond_ex_fwd / _bwd``"""
-
-    @staticmethod
-    def forward(ctx, h, eps, pm, pl, coeff, mode, s_):
-        lib = _lib.load()
-        b, n = eps.shape
-        z = torch.empty_like(eps)
-        loss = torch.empty(b, device=h.device, dtype=torch.float32)
-        check(lib.otvae_gaussian_prior_cond_ex_fwd(ptr(h), ptr(eps), ptr(pm), ptr(pl), b, s_, n // s_, float(coeff), int(mode), ptr(z),
-                                                   ptr(loss), stream()), "otvae_gaussian_prior_cond_ex_fwd")
-        ctx.save_for_backward(h, eps, pm, pl)
-        ctx.cfg = (float(coeff), int(mode), int(s_))
-        ctx.set_materialize_grads(False)
-        return z, loss
-
-    @staticmethod
-    def backward(ctx, gz, gloss):
-        if gz is None and gloss is None:
-            return (None,) * 7
-        h, eps, pm, pl = ctx.saved_tensors
-        coeff, mode, s_ = ctx.cfg
-        b, n = eps.shape
-        gz = gz.contiguous() if gz is not None else None
-        gloss = gloss.contiguous() if gloss is not None else None
-        gh = torch.empty_like(h)
-        gpm = torch.empty_like(pm) if ctx.needs_input_grad[2] else None
-        gpl = torch.empty_like(pl) if ctx.needs_input_grad[3] else None
-        check(_lib.load().otvae_gaussian_prior_cond_ex_bwd(ptr(h), ptr(eps), ptr(pm), ptr(pl), ptr(gz), ptr(gloss), b, s_, n // s_, coeff,
-                                                           mode, ptr(gh), ptr(gpm), ptr(gpl), stream()), "otvae_gaussian_prior_cond_ex_bwd")
-        return gh, None, gpm, gpl, None, None, None
-
-
-def gaussian_prior_conditional_ex(h: Tensor, eps: Tensor, prior_mean: Tensor, prior_log_std: Tensor, coeff: float,
-                                  empirical_kl: bool = False, fixed_var: bool = False, reparam_dim: int = 1):
-    """(z, coeff * loss[B]) of ``ConditionalGaussianPrior`` with the options it inherits (prior/conditional_gaussian.py:84-93): the prior
-    rows [B, prod(dim)] are laid out like z."""
-    _lib.require_cuda(h, "prior input")
-    b = h.shape[0]
-    s_, out_shape = _reparam_layout(h, reparam_dim, fixed_var)
-    flat = lambda t: t.contiguous().reshape(b, -1).float()  # noqa: E731
-    mode = (1 if empirical_kl else 0) | (2 if fixed_var else 0)
-    z, loss = _CondGaussianPriorExFn.apply(flat(h), flat(eps), flat(prior_mean), flat(prior_log_std), float(coeff), mode, s_)
+    z, loss = _GaussianPriorFn.apply(flat(h), flat(eps), temp, flat(prior_mean), flat(prior_log_std), float(coeff), mode, s_)
     return z.reshape(out_shape), loss
 
 

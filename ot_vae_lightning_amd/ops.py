@@ -213,7 +213,7 @@ def _gp_fwd(h: Tensor, eps: Tensor, coeff: float):
     d, s = c2 // 2, hh * ww
     z = _nhwc(b, d, hh, ww, h)
     loss = torch.empty(b, device=h.device, dtype=torch.float32)
-    check(lib.otvae_gaussian_prior_fwd(ptr(h), ptr(eps), b, s, d, float(coeff), ptr(z), ptr(loss), stream()),
+    check(lib.otvae_gaussian_prior_fwd(ptr(h), ptr(eps), None, None, None, b, s, d, float(coeff), 0, ptr(z), ptr(loss), stream()),
           "otvae_gaussian_prior_fwd")
     return z, loss
 
@@ -226,8 +226,8 @@ def _gp_bwd(h: Tensor, eps: Tensor, gz: Optional[Tensor], gloss: Optional[Tensor
     gz = as_nhwc(gz) if gz is not None else None
     gloss = gloss.contiguous() if gloss is not None else None
     gh = torch.empty_strided(h.shape, h.stride(), device=h.device, dtype=h.dtype)
-    check(lib.otvae_gaussian_prior_bwd(ptr(h), ptr(eps), ptr(gz), ptr(gloss), b, s, d, float(coeff), ptr(gh), stream()),
-          "otvae_gaussian_prior_bwd")
+    check(lib.otvae_gaussian_prior_bwd(ptr(h), ptr(eps), None, None, None, ptr(gz), ptr(gloss), b, s, d, float(coeff), 0, ptr(gh),
+                                       None, None, stream()), "otvae_gaussian_prior_bwd")
     return gh
 
 

@@ -48,10 +48,8 @@ class ConditionalGaussianPrior(GaussianPrior, utils.DDPMixin):
             eps = torch.randn(shape, device=x.device, dtype=x.dtype)
         # [B, prod(dim)] rows of the class embeddings (nn.Embedding's lookup with the library's deterministic backward)
         pm, pl = HF.embedding(self._mu.weight, labels), HF.embedding(self._log_std.weight, labels)
-        if self.fixed_var or self.empirical_kl or self.reparam_dim not in (1, 1 - x.dim()):
-            z, loss = HF.gaussian_prior_conditional_ex(x, eps, pm, pl, coeff, self.empirical_kl, self.fixed_var, self.reparam_dim)
-        else:
-            z, loss = HF.gaussian_prior_conditional(x, eps, pm, pl, coeff)
+        z, loss = HF.gaussian_prior_general(x, eps, coeff, prior_mean=pm, prior_log_std=pl, empirical_kl=self.empirical_kl,
+                                            fixed_var=self.fixed_var, reparam_dim=self.reparam_dim)
         q = self.reparametrization(x.detach())
         if self.decay is not None and self.decay > 0 and self.training:
             self.ema_update(q, labels)

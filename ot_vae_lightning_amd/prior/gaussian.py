@@ -64,8 +64,9 @@ class GaussianPrior(Prior):
         if eps is None:
             eps = torch.randn(shape, device=x.device, dtype=x.dtype)
         if self.fixed_var or self.empirical_kl or self.reparam_dim not in (1, 1 - x.dim()):
-            z, loss = HF.gaussian_prior_ex(x, eps, coeff, self.empirical_kl, self.fixed_var, time, self.reparam_dim)
-        else:
+            z, loss = HF.gaussian_prior_general(x, eps, coeff, empirical_kl=self.empirical_kl, fixed_var=self.fixed_var,
+                                                temperature=time, reparam_dim=self.reparam_dim)
+        else:   # the default options: the custom op reads channels-last maps in place
             z, loss = HF.gaussian_prior(x, eps, coeff)
         zd = z.detach()  # the lazily built distributions must not keep this step's autograd graph alive
         artifacts = {"prior": _LazyNormal(lambda: torch.zeros_like(zd), lambda: torch.ones_like(zd)),

@@ -632,7 +632,7 @@ def test_gaussian_prior_vs_reference_golden(A, tag):
 @pytest.mark.parametrize("tag", ["empirical", "fixed_var", "fixed_var_time", "fixed_var_empirical"])
 def test_gaussian_prior_options_vs_reference_golden(A, tag):
     """``GaussianPrior(empirical_kl=, fixed_var=)`` and the temperature of ``encode(time=)`` (reference
-    prior/gaussian.py:38-41,63-96; prior/base.py:65-68) on ``otvae_gaussian_prior_ex_fwd / _bwd``."""
+    prior/gaussian.py:38-41,63-96; prior/base.py:65-68) on ``otvae_gaussian_prior_fwd / _bwd``."""
     g = group(load_golden("prior.npz"), tag)
     coeff, emp, fixed = g["cfg"].tolist()
     rep = Report(f"GaussianPrior options ({tag}) vs reference golden")
