@@ -257,11 +257,15 @@ int otvae_attn_stage_bwd_slots(const float* gy, const float* wproj, const float*
 /* Element-wise dropout with the same counter-based masks (keep(row, col) of a [rows][D] tensor, D % 4 == 0), optionally
  * fused with the ReLU in front of it: y = keep ? act(x)/(1-p) : 0.  relu != 0: the dropout(relu(linear1(x))) of a training-
  * mode nn.TransformerEncoderLayer; relu == 0: PositionalEmbedding's embedding dropout (networks/vit.py:54-58).  The backward
- * recomputes the mask from used[0] and reads x for the ReLU gate; otvae_layernorm_dropout_mask returns the same mask. */
+ * recomputes the mask from used[0] and reads x for the ReLU gate. */
 int otvae_dropout_fwd(const float* x, int64_t rows, int D, int relu, float p, const int64_t* key, int stream_id, float* y,
                       int64_t* used, void* stream);
 int otvae_dropout_bwd(const float* x, const float* gy, int64_t rows, int D, int relu, float p, const int64_t* used, float* gx,
                       void* stream);
+/* keep[row*cols + col] = 1 iff the hashed dropout of the call that left `used` keeps (row, col); uint8 [rows][cols].
+ * row / col are what the producing kernel hashes: attention (slice*Tq + query, key token); LayerNorm and token
+ * dropout (row, column); dropout2d (n, c).  Test and debugging aid. */
+int otvae_dropout_keep_mask(int64_t rows, int cols, float p, const int64_t* used, uint8_t* keep, void* stream);
 
 /* Self-attention with dropout on the attention probabilities: nn.MultiheadAttention(dropout=p) in training mode, which is
  * how the reference's ViT builds every layer (networks/vit.py:157-172 hand `dropout` to nn.TransformerEncoderLayer;
@@ -269,15 +273,13 @@ int otvae_dropout_bwd(const float* x, const float* gy, int64_t rows, int D, int 
  * The T x T mask is never stored: keep[t][s] is a counter-based hash of (call key, slice, t, s) that the backward pass
  * recomputes.  key: device int64[2] {seed, call counter} -- device memory, so that a captured hipGraph draws a fresh mask
  * on every replay once the host bumps the counter with a captured add; stream_id (0..4094) tells call sites apart.  The
- * forward writes the call key it derived to used[0] (device int64[1]); the backward and _mask read it from there.
+ * forward writes the call key it derived to used[0] (device int64[1]); the backward reads it from there.
  * causal != 0 restricts the softmax of token t to tokens s <= t (the ViT's `causal_mask`, networks/vit.py:215-217); p may
- * then be 0.  lse is the natural log of the UN-dropped row sums.  T <= 256 and T*(2C+3) <= 16384; C in {1,2,4,8,16,32}.
- * otvae_attn_dropout_mask writes keep as uint8 [N][H][T][T] (test / debugging aid). */
+ * then be 0.  lse is the natural log of the UN-dropped row sums.  T <= 256 and T*(2C+3) <= 16384; C in {1,2,4,8,16,32}. */
 int otvae_attn_dropout_fwd(const float* qkv, int N, int T, int H, int C, float scale, float p, int causal, const int64_t* key,
                            int stream_id, float* out, float* lse, int64_t* used, void* stream);
 int otvae_attn_dropout_bwd(const float* qkv, const float* out, const float* lse, const float* gout, int N, int T, int H,
                            int C, float scale, float p, int causal, const int64_t* used, float* gqkv, void* stream);
-int otvae_attn_dropout_mask(int N, int T, int H, float p, const int64_t* used, uint8_t* keep, void* stream);
 /* Cross-attention: nn.MultiheadAttention(query, memory, memory) inside the nn.TransformerDecoderLayer of the ViT's
  * `preprocess_depth` variant (networks/vit.py:171-181, 240-244): Tq queries of one token set against Tk keys / values of another,
  * scores = scale * q.k, the same dropout on the probabilities as above (p may be 0: key / used may then be NULL).  q, k and v
@@ -292,32 +294,26 @@ int otvae_attn_cross_bwd(const float* q, int64_t q_img_stride, int q_row_stride,
                          int Tq, int Tk, int H, int C, float scale, float p, const int64_t* used, float* gq,
                          int64_t gq_img_stride, int gq_row_stride, float* gk, float* gv, int64_t gkv_img_stride,
                          int gkv_row_stride, void* stream);
-/* keep as uint8 [N][H][Tq][Tk] of the cross-attention call whose forward left `used` (test / debugging aid) */
-int otvae_attn_cross_mask(int N, int Tq, int Tk, int H, float p, const int64_t* used, uint8_t* keep, void* stream);
 
 /* ---- LayerNorm over the last dimension (the token streams of the ViT: networks/vit.py:38,54 and the two norms of each
  * nn.TransformerEncoderLayer, :169-172; torch.nn.functional.layer_norm arithmetic) ---------------------------------------
  * y[m][:] = (s - mean(s)) * rstd(s) * gamma + beta with s = x[m][:] + res[m][:] (res nullable: the "x + sublayer(x)" of the
  * post-norm block summed in; s is written to sum_out [M][D], which otvae_layernorm_bwd takes as xs; without a residual
  * sum_out may be NULL and xs = x).  mean / rstd [M] are saved for backward.  D <= 2048.
- * Backward: gx [M][D] (the gradient of both x and res), dgamma / dbeta [D]; ws: otvae_layernorm_bwd_ws(M, D) floats. */
+ * key != NULL: the "x + dropout(sublayer(x))" of a training-mode nn.TransformerEncoderLayer (networks/vit.py:157-172 with
+ * dropout > 0) folded into the same kernels: s = res + x o keep / (1-p), 0 <= p < 1.  keep(row, col) is the counter-based hash of
+ * otvae_attn_dropout_* (key = device int64[2] {seed, call counter}, stream_id 0..4094 per call site, the forward leaves its call
+ * key in used[0]); nothing but s is stored; res, sum_out and used are then required.  key == NULL: p must be 0, used may be NULL.
+ * Backward: gx [M][D] = dL/ds, dgamma / dbeta [D]; ws: otvae_layernorm_bwd_ws(M, D) floats.  used == NULL (p = 0, gx_dropped NULL):
+ * gx is the gradient of both x and res.  used = the forward's: gx is the residual's gradient and gx_dropped = gx o keep / (1-p)
+ * the sublayer output's. */
 int otvae_layernorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, int M, int D, float eps,
-                        float* sum_out, float* y, float* mean, float* rstd, void* stream);
+                        float p, const int64_t* key, int stream_id, float* sum_out, float* y, float* mean, float* rstd,
+                        int64_t* used, void* stream);
 int otvae_layernorm_bwd_ws(int M, int D);
 int otvae_layernorm_bwd(const float* xs, const float* gy, const float* gamma, const float* mean, const float* rstd, int M, int D,
-                        float* gx, float* dgamma, float* dbeta, float* ws, void* stream);
-/* The "x + dropout(sublayer(x))" of a training-mode nn.TransformerEncoderLayer (networks/vit.py:157-172 with dropout > 0)
- * folded into the same kernels: s = res + x o keep / (1-p), y = LayerNorm(s).  keep(row, col) is the counter-based hash of
- * otvae_attn_dropout_* (key = device int64[2] {seed, call counter}, stream_id per call site, the forward leaves its call key
- * in used[0]); nothing but s is stored.  The backward returns gx = dL/ds (the residual's gradient) and
- * gx_dropped = gx o keep / (1-p) (the sublayer output's).  otvae_layernorm_dropout_mask: keep as uint8 [M][D] (test aid). */
-int otvae_layernorm_dropout_fwd(const float* x, const float* res, const float* gamma, const float* beta, int M, int D,
-                                float eps, float p, const int64_t* key, int stream_id, float* sum_out, float* y, float* mean,
-                                float* rstd, int64_t* used, void* stream);
-int otvae_layernorm_dropout_bwd(const float* xs, const float* gy, const float* gamma, const float* mean, const float* rstd,
-                                int M, int D, float p, const int64_t* used, float* gx, float* gx_dropped, float* dgamma,
-                                float* dbeta, float* ws, void* stream);
-int otvae_layernorm_dropout_mask(int M, int D, float p, const int64_t* used, uint8_t* keep, void* stream);
+                        float p, const int64_t* used, float* gx, float* gx_dropped, float* dgamma, float* dbeta, float* ws,
+                        void* stream);
 
 /* ---- GaussianPrior / ConditionalGaussianPrior (prior/gaussian.py:58-96, prior/conditional_gaussian.py:44-93) + Prior.forward
  * scaling (prior/base.py:74-78): re-parametrisation z = mu + eps sd and loss[B] = coeff * KL(q || p) in one pass, explicit backward.
@@ -395,11 +391,10 @@ int otvae_film_fwd(const float* x, const float* scale, const float* bias, int N,
 int otvae_film_bwd(const float* g, const float* x, const float* scale, int N, int HW, int C, float* gx, float* gscale, float* gbias,
                    void* stream);
 /* nn.Dropout2d(p): y = keep(n, c) ? x / (1 - p) : 0 with keep = hash(call key, n, c); key = device int64[2] {seed, call counter},
- * used[0] <- the call key (the backward and otvae_dropout2d_mask recompute the mask from it; no mask tensor) */
+ * used[0] <- the call key (the backward recomputes the mask from it; no mask tensor) */
 int otvae_dropout2d_fwd(const float* x, int N, int HW, int C, float p, const int64_t* key, int stream_id, float* y, int64_t* used,
                         void* stream);
 int otvae_dropout2d_bwd(const float* gy, int N, int HW, int C, float p, const int64_t* used, float* gx, void* stream);
-int otvae_dropout2d_mask(int N, int C, float p, const int64_t* used, uint8_t* keep, void* stream);
 
 /* ---- GaussianModel(update_with_autograd=True): log-density under N(mean, L L^T) / N(mean, diag(sigma^2))
  * (ot/distribution_models/gaussian_model.py:52-55,76-93,125-128; torch.distributions.MultivariateNormal(scale_tril=) /
@@ -414,52 +409,41 @@ int otvae_mvn_logprob_bwd(const double* g, const double* y, const double* L, int
                           void* stream);
 
 /* ---- Adam (model/vae.py:148-151; torch.optim.Adam defaults) over one flat buffer --------------------------- */
-/* hyper (device): float[4] = {lr, beta1, beta2, eps}; step (device int32) is the 1-based count of THIS update
- * (incremented by otvae_step_begin). grad_scale multiplies g first (1/world_size for data-parallel means). */
 /* dst[i][0..n[i]) = src[i][0..n[i]) for `count` contiguous fp32 ranges in one launch per 32 (pointer tables on the HOST, passed to the
  * kernel by value): the gradients autograd left in p.grad (embeddings, learned tokens) into their slots of the flat gradient buffer
  * that otvae_adam_step reads -- what the reference's optimizer finds in p.grad (model/vae.py:148-151). */
 int otvae_copy_batched(int count, const float* const* src, float* const* dst, const int64_t* n, void* stream);
 
-int otvae_step_begin(int32_t* step, void* stream);
-int otvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
-                    const int32_t* step, float grad_scale, void* stream);
-/* the same update with the gradient scale read from device memory (what otvae_grad_clip_coef leaves in out[0]) */
-int otvae_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
-                        const int32_t* step, const float* grad_scale_dev, void* stream);
-/* Guarded update: what makes a bad step survivable inside a captured training step (the reference leans on Lightning's
- * loop to stop on a NaN loss, configs/ddp.yaml:1-5; a hipGraph replay has no host in the loop).  The update is applied only
- * when every watched device scalar is finite: watch_loss[0] (the step's loss; a starved Sinkhorn solve poisons it with
- * NaN), and grad_scale_dev[0..1] = {scale, |g|} when given (what otvae_grad_clip_coef leaves; with max_norm <= 0 it only
- * reports the norm).  grad_scale_dev NULL: the host value grad_scale is used.  A skipped step leaves p, m, v unchanged, takes
- * *step back by one, restores state[n_state] from backup (below), and counts itself: guard[0] += 1, guard[1] = the step number
- * that was skipped (device int32[2]). */
-int otvae_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int32_t* step,
-                            float grad_scale, const float* grad_scale_dev, const float* watch_loss, int32_t* guard,
-                            float* state, const float* backup, int64_t n_state, void* stream);
-/* The superset entry: otvae_adam_step_guarded's arguments (guard / watch_loss / state may be NULL: unguarded) plus the parameter
- * moving average of the reference's `ema_decay` option (model/base.py:99,153-190; kept there by the third-party torch_ema package,
- * requirements.txt:10, unpinned): ema_shadow[n] -= (1 - d) (ema_shadow - p_new), d = min(ema_decay, (1 + t) / (10 + t)) with t the
- * device step counter (one update per accepted optimizer step), in the optimizer's own pass.  A refused step leaves the shadow alone. */
-int otvae_adam_step_ema(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int32_t* step,
-                        float grad_scale, const float* grad_scale_dev, const float* watch_loss, int32_t* guard, float* state,
-                        const float* backup, int64_t n_state, float* ema_shadow, double ema_decay, void* stream);
+/* The start of a step as ONE launch: *step += 1 (device int32, the 1-based count of the update this step ends in), the step guard's
+ * backup (n > 0: state[n], every running buffer of the model as one flat fp32 range, is copied to backup; a refused step copies it
+ * back) and the zeroing of `zero_words` int64 words (the BatchNorm statistic slots the step's kernels add into; 16-byte aligned, an
+ * even count, may be 0).  otvae_zero_words: the zeroing alone. */
+int otvae_step_begin(int32_t* step, const float* state, float* backup, int64_t n, void* zero, int64_t zero_words, void* stream);
+/* hyper (device): float[4] = {lr, beta1, beta2, eps}; step: the counter otvae_step_begin incremented.  g is multiplied by
+ * grad_scale first (1/world_size for data-parallel means), or by grad_scale_dev[0] when given (what otvae_grad_clip_coef leaves).
+ * Guarded update (guard != NULL; watch_loss and state need it): what makes a bad step survivable inside a captured training step (the
+ * reference leans on Lightning's loop to stop on a NaN loss, configs/ddp.yaml:1-5; a hipGraph replay has no host in the loop).  The
+ * update is applied only when every watched device scalar is finite: watch_loss[0] (the step's loss; a starved Sinkhorn solve poisons it
+ * with NaN; nullable), and grad_scale_dev[0..1] = {scale, |g|} when given (with max_norm <= 0 otvae_grad_clip_coef only reports the
+ * norm).  A skipped step leaves p, m, v unchanged, takes *step back by one, restores state[n_state] from backup (a NaN that reaches a
+ * BatchNorm does not stay one -- the next ReLU maps the NaN-normalised tensor to zeros -- so later layers would fold finite but
+ * meaningless batch statistics into their running buffers; n_state 0: no such buffers), and counts itself: guard[0] += 1, guard[1] =
+ * the step number that was skipped (device int32[2]).
+ * ema_shadow (nullable): the parameter moving average of the reference's `ema_decay` option (model/base.py:99,153-190; kept there by
+ * the third-party torch_ema package, requirements.txt:10, unpinned): ema_shadow[n] -= (1 - d) (ema_shadow - p_new), d = min(ema_decay,
+ * (1 + t) / (10 + t)) with t the device step counter (one update per accepted optimizer step), in the optimizer's own pass.  A refused
+ * step leaves the shadow alone. */
+int otvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int32_t* step,
+                    float grad_scale, const float* grad_scale_dev, const float* watch_loss, int32_t* guard, float* state,
+                    const float* backup, int64_t n_state, float* ema_shadow, double ema_decay, void* stream);
 /* The same moving-average update alone, with the caller's effective decay (a stock optimizer stepped by the reference's own loop) */
 int otvae_ema_update(float* shadow, const float* p, int64_t n, double decay, void* stream);
-/* The running buffers of a guarded step.  A NaN that reaches a BatchNorm does not stay one (the next ReLU maps the NaN-normalised
- * tensor to zeros), so later layers would fold finite but meaningless batch statistics into their running buffers:
- * otvae_step_begin_guarded increments *step like otvae_step_begin AND copies state[n_state] (every running buffer of the model,
- * one flat fp32 range) to backup; a refused step (otvae_adam_step_guarded) copies it back.  n_state 0: no such buffers. */
-int otvae_step_begin_guarded(int32_t* step, const float* state, float* backup, int64_t n_state, void* stream);
-/* Round 4: counter + (n > 0) the guard's backup + the zeroing of `zero_words` int64 words (the BatchNorm statistic slots the step's
- * kernels add into; 16-byte aligned, an even count, may be 0) as ONE launch.  otvae_zero_words: the zeroing alone. */
-int otvae_step_begin_slots(int32_t* step, const float* state, float* backup, int64_t n, void* zero, int64_t zero_words, void* stream);
 int otvae_zero_words(void* zero, int64_t zero_words, void* stream);
 
 /* ---- global-norm gradient clipping (configs/ddp.yaml:4 `gradient_clip_val: 1.0`, applied by Lightning through
  * torch.nn.utils.clip_grad_norm_) over the flat gradient buffer -------------------------------------------------- */
 /* g[n] holds the gradient SUM over ranks, grad_scale = 1/world_size.  norm = |g * grad_scale|_2 (fp64 accumulation);
- * out[0] = grad_scale * min(1, max_norm / (norm + 1e-6)) = the scale otvae_adam_step_dev applies to g; out[1] = norm.
+ * out[0] = grad_scale * min(1, max_norm / (norm + 1e-6)) = the scale otvae_adam_step applies to g (grad_scale_dev); out[1] = norm.
  * max_norm <= 0: no clipping (out[0] = grad_scale).  ws: otvae_grad_clip_ws() doubles. */
 int otvae_grad_clip_ws(void);
 int otvae_grad_clip_coef(const float* g, int64_t n, float grad_scale, float max_norm, double* ws, float* out,

@@ -90,19 +90,15 @@ SIGNATURES = {
     "otvae_attn_stage_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
     "otvae_attn_dropout_fwd": (i32, [vp, i32, i32, i32, i32, f32, f32, i32, vp, i32, vp, vp, vp, vp]),
     "otvae_attn_dropout_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp]),
-    "otvae_attn_dropout_mask": (i32, [i32, i32, i32, f32, vp, vp, vp]),
     "otvae_attn_cross_fwd": (i32, [vp, i64, i32, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, f32, vp, i32, vp, vp, vp, vp]),
-    "otvae_attn_cross_mask": (i32, [i32, i32, i32, i32, f32, vp, vp, vp]),
     "otvae_attn_cross_bwd": (i32, [vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, i64, i32,
                                    vp, vp, i64, i32, vp]),
-    "otvae_layernorm_fwd": (i32, [vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]),
+    "otvae_layernorm_fwd": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, i32, vp, vp, vp, vp, vp, vp]),
     "otvae_layernorm_bwd_ws": (i32, [i32, i32]),
-    "otvae_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
-    "otvae_layernorm_dropout_fwd": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, vp, i32, vp, vp, vp, vp, vp, vp]),
-    "otvae_layernorm_dropout_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
-    "otvae_layernorm_dropout_mask": (i32, [i32, i32, f32, vp, vp, vp]),
+    "otvae_layernorm_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
     "otvae_dropout_fwd": (i32, [vp, i64, i32, i32, f32, vp, i32, vp, vp, vp]),
     "otvae_dropout_bwd": (i32, [vp, vp, i64, i32, i32, f32, vp, vp, vp]),
+    "otvae_dropout_keep_mask": (i32, [i64, i32, f32, vp, vp, vp]),
     "otvae_gaussian_prior_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp]),
     "otvae_gaussian_prior_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
     "otvae_copy_batched": (i32, [i32, vp, vp, vp, vp]),
@@ -123,17 +119,11 @@ SIGNATURES = {
     "otvae_film_bwd": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "otvae_dropout2d_fwd": (i32, [vp, i32, i32, i32, f32, vp, i32, vp, vp, vp]),
     "otvae_dropout2d_bwd": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
-    "otvae_dropout2d_mask": (i32, [i32, i32, f32, vp, vp, vp]),
     "otvae_mvn_logprob_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "otvae_mvn_logprob_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-    "otvae_step_begin": (i32, [vp, vp]),
-    "otvae_adam_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp]),
-    "otvae_adam_step_dev": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp]),
-    "otvae_adam_step_ema": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, vp, vp, i64, vp, f64, vp]),
+    "otvae_adam_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, vp, vp, i64, vp, f64, vp]),
     "otvae_ema_update": (i32, [vp, vp, i64, f64, vp]),
-    "otvae_adam_step_guarded": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, vp, vp, i64, vp]),
-    "otvae_step_begin_guarded": (i32, [vp, vp, vp, i64, vp]),
-    "otvae_step_begin_slots": (i32, [vp, vp, vp, i64, vp, i64, vp]),
+    "otvae_step_begin": (i32, [vp, vp, vp, i64, vp, i64, vp]),
     "otvae_zero_words": (i32, [vp, i64, vp]),
     "otvae_grad_clip_ws": (i32, []),
     "otvae_grad_clip_coef": (i32, [vp, i64, f32, f32, vp, vp, vp]),

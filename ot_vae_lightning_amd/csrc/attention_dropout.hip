@@ -222,15 +222,6 @@ __global__ __launch_bounds__(256) void attn_drop_bwd_kernel(AttnIn in, const flo
     }
 }
 
-__global__ __launch_bounds__(256) void attn_drop_mask_kernel(long rows, int T, uint32_t thresh, const int64_t* __restrict__ used,
-                                                             uint8_t* __restrict__ keep) {
-    const uint64_t ck = (uint64_t)used[0];
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= rows * T) return;
-    const long row = e / T;
-    keep[e] = keep_pair(row_hash(ck, (uint32_t)row), (int)(e - row * T), thresh) ? 1 : 0;
-}
-
 static int adrop_plan(const char* who, int N, int Tq, int Tk, int H, int C, float p, int rs, int* spb, uint32_t* thresh) {
     OTVAE_REQUIRE(N > 0 && Tq > 0 && Tk > 0 && H > 0 && C > 0, "%s: bad sizes", who);
     OTVAE_REQUIRE(p >= 0.f && p < 1.f, "%s: dropout probability must be in [0, 1)", who);
@@ -347,28 +338,4 @@ extern "C" int otvae_attn_cross_bwd(const float* q, int64_t q_img_stride, int q_
     const AttnIn in = {q, k, v, (long)q_img_stride, (long)kv_img_stride, q_row_stride, kv_row_stride};
     const AttnGrad gr = {gq, gk, gv, (long)gq_img_stride, (long)gkv_img_stride, gq_row_stride, gkv_row_stride};
     return attn_general_bwd("otvae_attn_cross_bwd", in, out, lse, gout, N, Tq, Tk, H, C, scale, p, 0, used, gr, stream);
-}
-
-extern "C" int otvae_attn_dropout_mask(int N, int T, int H, float p, const int64_t* used, uint8_t* keep, void* stream) {
-    OTVAE_REQUIRE(used && keep, "otvae_attn_dropout_mask: NULL tensor");
-    int spb;
-    uint32_t thresh;
-    int rc = adrop_plan("otvae_attn_dropout_mask", N, T, T, H, 1, p, 5, &spb, &thresh);
-    if (rc) return rc;
-    const long rows = (long)N * H * T;
-    attn_drop_mask_kernel<<<(int)cdiv((int64_t)rows * T, 256), 256, 0, (hipStream_t)stream>>>(rows, T, thresh, used, keep);
-    OTVAE_CHECK_LAUNCH("otvae_attn_dropout_mask");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_attn_cross_mask(int N, int Tq, int Tk, int H, float p, const int64_t* used, uint8_t* keep, void* stream) {
-    OTVAE_REQUIRE(used && keep, "otvae_attn_cross_mask: NULL tensor");
-    int spb;
-    uint32_t thresh;
-    int rc = adrop_plan("otvae_attn_cross_mask", N, Tq, Tk, H, 1, p, 5, &spb, &thresh);
-    if (rc) return rc;
-    const long rows = (long)N * H * Tq;
-    attn_drop_mask_kernel<<<(int)cdiv((int64_t)rows * Tk, 256), 256, 0, (hipStream_t)stream>>>(rows, Tk, thresh, used, keep);
-    OTVAE_CHECK_LAUNCH("otvae_attn_cross_mask");
-    return OTVAE_OK;
 }

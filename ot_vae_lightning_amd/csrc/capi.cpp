@@ -15,7 +15,7 @@ void otvae_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* otvae_last_error(void) { return g_err; }
-extern "C" int otvae_abi_version(void) { return 1; }
+extern "C" int otvae_abi_version(void) { return 2; }
 
 extern "C" int otvae_device_info(int* n_cu, int* wave_size, char* arch, int arch_len) {
     int dev = 0;

@@ -3,6 +3,7 @@
 // -- the "dropout(activation(linear1(x)))" in the feed-forward half of a training-mode nn.TransformerEncoderLayer and the
 // embedding dropout of PositionalEmbedding (reference networks/vit.py:54-58,157-172).  No mask tensor exists: the backward
 // kernel recomputes keep from the call key the forward left in `used`, and reads x for the ReLU gate.
+// otvae_dropout_keep_mask writes out the mask of any kernel that drops with this hash (test and debugging aid).
 #include "common.h"
 #include "dropout_hash.h"
 
@@ -77,5 +78,26 @@ extern "C" int otvae_dropout_bwd(const float* x, const float* gy, int64_t rows, 
     if (relu) dropout_kernel<true, true><<<dropout_grid(total), 256, 0, st>>>(x, gy, total, D, th, ik, used, 0, nullptr, gx);
     else dropout_kernel<false, true><<<dropout_grid(total), 256, 0, st>>>(x, gy, total, D, th, ik, used, 0, nullptr, gx);
     OTVAE_CHECK_LAUNCH("otvae_dropout_bwd");
+    return OTVAE_OK;
+}
+
+// keep[row][col] of the call that left `used`, for every kernel that drops with dropout_hash.h: (row, col) as that kernel hashes them
+__global__ __launch_bounds__(256) void dropout_keep_mask_kernel(int64_t total, int cols, uint32_t thresh, const int64_t* __restrict__ used,
+                                                                uint8_t* __restrict__ keep) {
+    const uint64_t ck = (uint64_t)used[0];
+    for (int64_t e = blockIdx.x * (int64_t)256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t row = e / cols;
+        keep[e] = keep_pair(row_hash(ck, (uint32_t)row), (int)(e - row * cols), thresh) ? 1 : 0;
+    }
+}
+
+extern "C" int otvae_dropout_keep_mask(int64_t rows, int cols, float p, const int64_t* used, uint8_t* keep, void* stream) {
+    OTVAE_REQUIRE(used && keep, "otvae_dropout_keep_mask: NULL tensor");
+    OTVAE_REQUIRE(rows > 0 && cols > 0 && rows < ((int64_t)1 << 32), "otvae_dropout_keep_mask: bad sizes (rows must stay below 2^32)");
+    OTVAE_REQUIRE(p >= 0.f && p < 1.f, "otvae_dropout_keep_mask: dropout probability must be in [0, 1)");
+    const int64_t total = rows * cols, blocks = (total + 255) / 256;
+    dropout_keep_mask_kernel<<<(int)(blocks < 4096 ? blocks : 4096), 256, 0, (hipStream_t)stream>>>(total, cols, dropout_threshold(p), used,
+                                                                                                  keep);
+    OTVAE_CHECK_LAUNCH("otvae_dropout_keep_mask");
     return OTVAE_OK;
 }

@@ -72,13 +72,6 @@ __global__ __launch_bounds__(256) void dropout2d_kernel(const float* __restrict_
     }
 }
 
-__global__ __launch_bounds__(256) void dropout2d_mask_kernel(int N, int C, uint32_t thresh, const int64_t* __restrict__ used,
-                                                             uint8_t* __restrict__ keep) {
-    const uint64_t ck = (uint64_t)used[0];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < N * C) keep[i] = keep_pair(row_hash(ck, (uint32_t)(i / C)), i % C, thresh) ? 1 : 0;
-}
-
 extern "C" int otvae_dropout2d_fwd(const float* x, int N, int HW, int C, float p, const int64_t* key, int stream_id, float* y,
                                    int64_t* used, void* stream) {
     OTVAE_REQUIRE(x && y && key && used && N > 0 && HW > 0 && C > 0 && p >= 0.f && p < 1.f && stream_id >= 0 && stream_id < 4095,
@@ -96,12 +89,5 @@ extern "C" int otvae_dropout2d_bwd(const float* gy, int N, int HW, int C, float 
     dropout2d_kernel<true><<<imin(cdiv(total, 256), 4096), 256, 0, (hipStream_t)stream>>>(gy, total, HW * C, C, dropout_threshold(p),
                                                                                         1.f / (1.f - p), used, 0, nullptr, gx);
     OTVAE_CHECK_LAUNCH("otvae_dropout2d_bwd");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_dropout2d_mask(int N, int C, float p, const int64_t* used, uint8_t* keep, void* stream) {
-    OTVAE_REQUIRE(used && keep && N > 0 && C > 0 && p >= 0.f && p < 1.f, "otvae_dropout2d_mask: bad argument");
-    dropout2d_mask_kernel<<<cdiv(N * C, 256), 256, 0, (hipStream_t)stream>>>(N, C, dropout_threshold(p), used, keep);
-    OTVAE_CHECK_LAUNCH("otvae_dropout2d_mask");
     return OTVAE_OK;
 }

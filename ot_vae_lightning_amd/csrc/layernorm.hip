@@ -82,38 +82,35 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     }
 }
 
+// key == NULL: the plain instantiation (p must be 0, res / used optional); key != NULL: the DROP one
 extern "C" int otvae_layernorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, int M, int D, float eps,
-                                   float* sum_out, float* y, float* mean, float* rstd, void* stream) {
+                                   float p, const int64_t* key, int stream_id, float* sum_out, float* y, float* mean, float* rstd,
+                                   int64_t* used, void* stream) {
     OTVAE_REQUIRE(x && gamma && beta && y && mean && rstd && M > 0 && D > 0, "otvae_layernorm_fwd: bad argument");
+    OTVAE_REQUIRE(!res || sum_out, "otvae_layernorm_fwd: a residual needs sum_out (x + res is what backward reads)");
+    if (key) {
+        OTVAE_REQUIRE(res && used, "otvae_layernorm_fwd: dropout needs the residual the thinned x is added to, and `used`");
+        OTVAE_REQUIRE(p >= 0.f && p < 1.f && stream_id >= 0 && stream_id < 4095, "otvae_layernorm_fwd: bad p or stream_id");
+    } else {
+        OTVAE_REQUIRE(p == 0.f, "otvae_layernorm_fwd: dropout (p > 0) needs `key`");
+    }
     if (D > 64 * LN_MAXV) {
         otvae_set_error("otvae_layernorm_fwd: D = %d unsupported (D <= %d)", D, 64 * LN_MAXV);
         return OTVAE_EUNSUPPORTED;
     }
-    OTVAE_REQUIRE(!res || sum_out, "otvae_layernorm_fwd: a residual needs sum_out (x + res is what backward reads)");
     hipStream_t st = (hipStream_t)stream;
-#define LN_FWD(NV_) layernorm_fwd_kernel<NV_, false><<<cdiv(M, 4), 256, 0, st>>>(x, res, gamma, beta, M, D, eps, sum_out, y, mean, rstd, LnDrop{})
+    const LnDrop dr = key ? LnDrop{dropout_threshold(p), 1.f / (1.f - p), key, stream_id, used} : LnDrop{};
+#define LN_FWD_K(NV_, DROP_) \
+    layernorm_fwd_kernel<NV_, DROP_><<<cdiv(M, 4), 256, 0, st>>>(x, res, gamma, beta, M, D, eps, sum_out, y, mean, rstd, dr)
+#define LN_FWD(NV_)                       \
+    do {                                  \
+        if (key) LN_FWD_K(NV_, true);     \
+        else LN_FWD_K(NV_, false);        \
+    } while (0)
     LN_NV_SWITCH(D, LN_FWD)
 #undef LN_FWD
+#undef LN_FWD_K
     OTVAE_CHECK_LAUNCH("otvae_layernorm_fwd");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_layernorm_dropout_fwd(const float* x, const float* res, const float* gamma, const float* beta, int M, int D,
-                                           float eps, float p, const int64_t* key, int stream_id, float* sum_out, float* y, float* mean,
-                                           float* rstd, int64_t* used, void* stream) {
-    OTVAE_REQUIRE(x && res && gamma && beta && sum_out && y && mean && rstd && key && used && M > 0 && D > 0,
-                  "otvae_layernorm_dropout_fwd: bad argument (the residual and sum_out are required)");
-    OTVAE_REQUIRE(p >= 0.f && p < 1.f && stream_id >= 0 && stream_id < 4095, "otvae_layernorm_dropout_fwd: bad p or stream_id");
-    if (D > 64 * LN_MAXV) {
-        otvae_set_error("otvae_layernorm_dropout_fwd: D = %d unsupported (D <= %d)", D, 64 * LN_MAXV);
-        return OTVAE_EUNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const LnDrop dr = {dropout_threshold(p), 1.f / (1.f - p), key, stream_id, used};
-#define LN_FWD(NV_) layernorm_fwd_kernel<NV_, true><<<cdiv(M, 4), 256, 0, st>>>(x, res, gamma, beta, M, D, eps, sum_out, y, mean, rstd, dr)
-    LN_NV_SWITCH(D, LN_FWD)
-#undef LN_FWD
-    OTVAE_CHECK_LAUNCH("otvae_layernorm_dropout_fwd");
     return OTVAE_OK;
 }
 
@@ -213,61 +210,34 @@ extern "C" int otvae_layernorm_bwd_ws(int M, int D) {
     return cdiv(M, LN_ROWS_PER_BLOCK) * 2 * D * 2;  // floats (the partials are doubles; a torch fp32 allocation is 8-byte aligned)
 }
 
+// used == NULL: the plain instantiation (gx is the gradient of both x and res); otherwise the DROP one, which also writes gx_dropped
 extern "C" int otvae_layernorm_bwd(const float* xs, const float* gy, const float* gamma, const float* mean, const float* rstd, int M,
-                                   int D, float* gx, float* dgamma, float* dbeta, float* ws, void* stream) {
+                                   int D, float p, const int64_t* used, float* gx, float* gx_dropped, float* dgamma, float* dbeta,
+                                   float* ws, void* stream) {
     OTVAE_REQUIRE(xs && gy && gamma && mean && rstd && gx && dgamma && dbeta && ws && M > 0 && D > 0,
                   "otvae_layernorm_bwd: bad argument");
+    OTVAE_REQUIRE(used ? gx_dropped && p >= 0.f && p < 1.f : !gx_dropped && p == 0.f,
+                  "otvae_layernorm_bwd: `used`, gx_dropped and p in [0, 1) come together (dropout) or not at all (p = 0)");
     if (D > 64 * LN_MAXV || (size_t)2 * D * sizeof(double) > 64 * 1024) {
         otvae_set_error("otvae_layernorm_bwd: D = %d unsupported (D <= 2048)", D);
         return OTVAE_EUNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
     const int P = cdiv(M, LN_ROWS_PER_BLOCK);
-#define LN_BWD(NV_) \
-    layernorm_bwd_kernel<NV_, false><<<P, 256, (size_t)2 * D * sizeof(double), st>>>(xs, gy, gamma, mean, rstd, M, D, gx, (double*)ws, nullptr, LnDrop{})
+    const LnDrop dr = used ? LnDrop{dropout_threshold(p), 1.f / (1.f - p), used, 0, nullptr} : LnDrop{};
+#define LN_BWD_K(NV_, DROP_)                                                                                                              \
+    layernorm_bwd_kernel<NV_, DROP_><<<P, 256, (size_t)2 * D * sizeof(double), st>>>(xs, gy, gamma, mean, rstd, M, D, gx, (double*)ws, \
+                                                                                     gx_dropped, dr)
+#define LN_BWD(NV_)                       \
+    do {                                  \
+        if (used) LN_BWD_K(NV_, true);    \
+        else LN_BWD_K(NV_, false);        \
+    } while (0)
     LN_NV_SWITCH(D, LN_BWD)
 #undef LN_BWD
+#undef LN_BWD_K
     OTVAE_CHECK_LAUNCH("otvae_layernorm_bwd");
     layernorm_param_reduce_kernel<<<cdiv(2 * D, 16), 256, 0, st>>>((const double*)ws, P, D, dgamma, dbeta);
     OTVAE_CHECK_LAUNCH("otvae_layernorm_bwd(reduce)");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_layernorm_dropout_bwd(const float* xs, const float* gy, const float* gamma, const float* mean, const float* rstd,
-                                           int M, int D, float p, const int64_t* used, float* gx, float* gx_dropped, float* dgamma,
-                                           float* dbeta, float* ws, void* stream) {
-    OTVAE_REQUIRE(xs && gy && gamma && mean && rstd && used && gx && gx_dropped && dgamma && dbeta && ws && M > 0 && D > 0,
-                  "otvae_layernorm_dropout_bwd: bad argument");
-    OTVAE_REQUIRE(p >= 0.f && p < 1.f, "otvae_layernorm_dropout_bwd: dropout probability must be in [0, 1)");
-    if (D > 64 * LN_MAXV || (size_t)2 * D * sizeof(double) > 64 * 1024) {
-        otvae_set_error("otvae_layernorm_dropout_bwd: D = %d unsupported (D <= 2048)", D);
-        return OTVAE_EUNSUPPORTED;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int P = cdiv(M, LN_ROWS_PER_BLOCK);
-    const LnDrop dr = {dropout_threshold(p), 1.f / (1.f - p), used, 0, nullptr};
-#define LN_BWD(NV_) \
-    layernorm_bwd_kernel<NV_, true><<<P, 256, (size_t)2 * D * sizeof(double), st>>>(xs, gy, gamma, mean, rstd, M, D, gx, (double*)ws, gx_dropped, dr)
-    LN_NV_SWITCH(D, LN_BWD)
-#undef LN_BWD
-    OTVAE_CHECK_LAUNCH("otvae_layernorm_dropout_bwd");
-    layernorm_param_reduce_kernel<<<cdiv(2 * D, 16), 256, 0, st>>>((const double*)ws, P, D, dgamma, dbeta);
-    OTVAE_CHECK_LAUNCH("otvae_layernorm_dropout_bwd(reduce)");
-    return OTVAE_OK;
-}
-
-// keep mask of a otvae_layernorm_dropout_fwd call as uint8 [M][D] (test aid)
-__global__ __launch_bounds__(256) void layernorm_dropout_mask_kernel(int M, int D, uint32_t thresh, const int64_t* __restrict__ used,
-                                                                     uint8_t* __restrict__ keep) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= (long)M * D) return;
-    const int row = (int)(e / D);
-    keep[e] = keep_pair(row_hash((uint64_t)used[0], (uint32_t)row), (int)(e - (long)row * D), thresh) ? 1 : 0;
-}
-
-extern "C" int otvae_layernorm_dropout_mask(int M, int D, float p, const int64_t* used, uint8_t* keep, void* stream) {
-    OTVAE_REQUIRE(used && keep && M > 0 && D > 0 && p >= 0.f && p < 1.f, "otvae_layernorm_dropout_mask: bad argument");
-    layernorm_dropout_mask_kernel<<<(int)cdiv((int64_t)M * D, 256), 256, 0, (hipStream_t)stream>>>(M, D, dropout_threshold(p), used, keep);
-    OTVAE_CHECK_LAUNCH("otvae_layernorm_dropout_mask");
     return OTVAE_OK;
 }

@@ -273,14 +273,24 @@ extern "C" int otvae_copy_batched(int count, const float* const* src, float* con
     return OTVAE_OK;
 }
 
-// ---- Adam ----------------------------------------------------------------------------------------------------
-__global__ void step_begin_kernel(int32_t* step) {
+// ---- Adam and the start of its step ---------------------------------------------------------------------------
+// The start of a step as ONE launch: the step counter, the step guard's backup of the running state (n may be 0) and the zeroing of
+// the BatchNorm statistic slots the step's kernels will add into (functional.SlotArena; zero_words int64 words, 16-byte aligned, may be 0)
+__global__ __launch_bounds__(256) void step_begin_kernel(int32_t* step, const float* __restrict__ state, float* __restrict__ backup,
+                                                         int64_t n, int4* __restrict__ zero, int64_t zero_n16) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *step += 1;
+    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) backup[i] = state[i];
+    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < zero_n16; i += (int64_t)gridDim.x * 256) zero[i] = make_int4(0, 0, 0, 0);
 }
 
-extern "C" int otvae_step_begin(int32_t* step, void* stream) {
-    OTVAE_REQUIRE(step, "otvae_step_begin: NULL step");
-    step_begin_kernel<<<1, 64, 0, (hipStream_t)stream>>>(step);
+extern "C" int otvae_step_begin(int32_t* step, const float* state, float* backup, int64_t n, void* zero, int64_t zero_words,
+                                void* stream) {
+    OTVAE_REQUIRE(step && (n == 0 || (state && backup)) && n >= 0, "otvae_step_begin: bad argument");
+    OTVAE_REQUIRE(zero_words >= 0 && (zero_words == 0 || (zero && ((uintptr_t)zero & 15) == 0 && zero_words % 2 == 0)),
+                  "otvae_step_begin: the range to zero must be 16-byte aligned, an even number of int64 words");
+    const int64_t work = n > zero_words / 2 ? n : zero_words / 2;
+    step_begin_kernel<<<imax(1, imin(cdiv(work, 1024), 1024)), 256, 0, (hipStream_t)stream>>>(step, state, backup, n, (int4*)zero,
+                                                                                              zero_words / 2);
     OTVAE_CHECK_LAUNCH("otvae_step_begin");
     return OTVAE_OK;
 }
@@ -296,35 +306,22 @@ __device__ __forceinline__ float ema_step(float s, float p, float omd) {
 
 // torch.optim.Adam (no weight decay / amsgrad): m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
 // p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
-// Step guard, running buffers.  A NaN that reaches a BatchNorm's input does not stay a NaN: the next layer's ReLU (fmaxf) turns the
-// NaN-normalised tensor into zeros, so later layers see finite -- and meaningless -- batch statistics and would fold them into
-// their running buffers.  The guarded step therefore keeps a copy of all running buffers (one flat fp32 range) from the start
-// of the step (otvae_step_begin_guarded) and the guarded Adam kernel puts it back when it refuses the step.
-__global__ __launch_bounds__(256) void step_begin_guarded_kernel(int32_t* step, const float* __restrict__ state, float* __restrict__ backup,
-                                                                 int64_t n) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *step += 1;
-    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) backup[i] = state[i];
-}
-
-extern "C" int otvae_step_begin_guarded(int32_t* step, const float* state, float* backup, int64_t n, void* stream) {
-    OTVAE_REQUIRE(step && (n == 0 || (state && backup)) && n >= 0, "otvae_step_begin_guarded: bad argument");
-    step_begin_guarded_kernel<<<imax(1, imin(cdiv(n, 1024), 1024)), 256, 0, (hipStream_t)stream>>>(step, state, backup, n);
-    OTVAE_CHECK_LAUNCH("otvae_step_begin_guarded");
-    return OTVAE_OK;
-}
-
 // Step guard (guard != NULL): the update is applied only when every watched device scalar is finite -- the step's loss
 // (a starved Sinkhorn solve poisons it with NaN, csrc/sinkhorn.hip: sk_finish) and, when the gradient norm was reduced
 // (otvae_grad_clip_coef), that norm.  Every block evaluates the same two scalars, so the decision is uniform without a flag
 // kernel.  A skipped step leaves p, m, v untouched, takes the step counter back (Adam's bias correction must not advance) and
 // counts itself in guard[0]; guard[1] holds the step number of the last skip.
+// Step guard, running buffers.  A NaN that reaches a BatchNorm's input does not stay a NaN: the next layer's ReLU (fmaxf) turns the
+// NaN-normalised tensor into zeros, so later layers see finite -- and meaningless -- batch statistics and would fold them into
+// their running buffers.  The guarded step therefore keeps a copy of all running buffers (one flat fp32 range) from the start
+// of the step (otvae_step_begin) and the guarded Adam kernel puts it back when it refuses the step.
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, const float* __restrict__ hyper,
                                                    int32_t* __restrict__ step, float grad_scale,
                                                    const float* __restrict__ scale_dev, int32_t* __restrict__ guard,
                                                    const float* __restrict__ watch_loss, float* __restrict__ state,
                                                    const float* __restrict__ backup, int64_t n_state,
-                                                   float* __restrict__ ema = nullptr, double ema_decay = 0.0) {
+                                                   float* __restrict__ ema, double ema_decay) {
     if (scale_dev) grad_scale = *scale_dev;  // clip coefficient x 1/world, left by grad_clip_final_kernel
     if (guard) {
         bool ok = isfinite(grad_scale);
@@ -409,55 +406,20 @@ extern "C" int otvae_ema_update(float* shadow, const float* p, int64_t n, double
     return OTVAE_OK;
 }
 
-extern "C" int otvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
-                               const int32_t* step, float grad_scale, void* stream) {
+extern "C" int otvae_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int32_t* step,
+                               float grad_scale, const float* grad_scale_dev, const float* watch_loss, int32_t* guard,
+                               float* state, const float* backup, int64_t n_state, float* ema_shadow, double ema_decay,
+                               void* stream) {
     OTVAE_REQUIRE(p && g && m && v && hyper && step && n > 0, "otvae_adam_step: bad argument");
-    OTVAE_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0),
-                  "otvae_adam_step: buffers must be 16-byte aligned");
-    adam_kernel<<<imin(cdiv(n, 1024), 2048), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper, const_cast<int32_t*>(step), grad_scale,
-                                                                            nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-    OTVAE_CHECK_LAUNCH("otvae_adam_step");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
-                                   const int32_t* step, const float* grad_scale_dev, void* stream) {
-    OTVAE_REQUIRE(p && g && m && v && hyper && step && grad_scale_dev && n > 0, "otvae_adam_step_dev: bad argument");
-    OTVAE_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0),
-                  "otvae_adam_step_dev: buffers must be 16-byte aligned");
-    adam_kernel<<<imin(cdiv(n, 1024), 2048), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper, const_cast<int32_t*>(step), 1.f,
-                                                                            grad_scale_dev, nullptr, nullptr, nullptr, nullptr, 0);
-    OTVAE_CHECK_LAUNCH("otvae_adam_step_dev");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_adam_step_ema(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int32_t* step,
-                                   float grad_scale, const float* grad_scale_dev, const float* watch_loss, int32_t* guard,
-                                   float* state, const float* backup, int64_t n_state, float* ema_shadow, double ema_decay,
-                                   void* stream) {
-    OTVAE_REQUIRE(p && g && m && v && hyper && step && n > 0, "otvae_adam_step_ema: bad argument");
-    OTVAE_REQUIRE(n_state >= 0 && (n_state == 0 || (state && backup && guard)), "otvae_adam_step_ema: state / backup / guard missing");
-    OTVAE_REQUIRE(!watch_loss || guard, "otvae_adam_step_ema: a watched loss needs the guard counters");
-    OTVAE_REQUIRE(!ema_shadow || (ema_decay >= 0.0 && ema_decay <= 1.0), "otvae_adam_step_ema: ema_decay must lie in [0, 1]");
+    OTVAE_REQUIRE(n_state >= 0 && (n_state == 0 || (state && backup && guard)), "otvae_adam_step: state / backup / guard missing");
+    OTVAE_REQUIRE(!watch_loss || guard, "otvae_adam_step: a watched loss needs the guard counters");
+    OTVAE_REQUIRE(!ema_shadow || (ema_decay >= 0.0 && ema_decay <= 1.0), "otvae_adam_step: ema_decay must lie in [0, 1]");
     OTVAE_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
                       (!ema_shadow || (uintptr_t)ema_shadow % 16 == 0),
-                  "otvae_adam_step_ema: buffers must be 16-byte aligned");
+                  "otvae_adam_step: buffers must be 16-byte aligned");
     adam_kernel<<<imin(cdiv(n, 1024), 2048), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper, step, grad_scale, grad_scale_dev, guard,
                                                                             watch_loss, state, backup, n_state, ema_shadow, ema_decay);
-    OTVAE_CHECK_LAUNCH("otvae_adam_step_ema");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_adam_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int32_t* step,
-                                       float grad_scale, const float* grad_scale_dev, const float* watch_loss, int32_t* guard,
-                                       float* state, const float* backup, int64_t n_state, void* stream) {
-    OTVAE_REQUIRE(p && g && m && v && hyper && step && guard && n > 0, "otvae_adam_step_guarded: bad argument");
-    OTVAE_REQUIRE(n_state >= 0 && (n_state == 0 || (state && backup)), "otvae_adam_step_guarded: state / backup missing");
-    OTVAE_REQUIRE(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) && ((uintptr_t)v % 16 == 0),
-                  "otvae_adam_step_guarded: buffers must be 16-byte aligned");
-    adam_kernel<<<imin(cdiv(n, 1024), 2048), 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper, step, grad_scale, grad_scale_dev, guard,
-                                                                            watch_loss, state, backup, n_state);
-    OTVAE_CHECK_LAUNCH("otvae_adam_step_guarded");
+    OTVAE_CHECK_LAUNCH("otvae_adam_step");
     return OTVAE_OK;
 }
 
@@ -511,28 +473,6 @@ extern "C" int otvae_grad_clip_coef(const float* g, int64_t n, float grad_scale,
     OTVAE_CHECK_LAUNCH("otvae_grad_clip_coef(partial)");
     grad_clip_final_kernel<<<1, 256, 0, st>>>(ws, parts, grad_scale, max_norm, out);
     OTVAE_CHECK_LAUNCH("otvae_grad_clip_coef(final)");
-    return OTVAE_OK;
-}
-
-// ---- start of a step, round 4: the step counter, the step guard's backup of the running state (n may be 0) and the zeroing of the
-// BatchNorm statistic slots the step's kernels will add into (functional.SlotArena; zero_words int64 words, 16-byte aligned, may be 0)
-// as ONE launch
-__global__ __launch_bounds__(256) void step_begin_slots_kernel(int32_t* step, const float* __restrict__ state, float* __restrict__ backup,
-                                                               int64_t n, int4* __restrict__ zero, int64_t zero_n16) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *step += 1;
-    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) backup[i] = state[i];
-    for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < zero_n16; i += (int64_t)gridDim.x * 256) zero[i] = make_int4(0, 0, 0, 0);
-}
-
-extern "C" int otvae_step_begin_slots(int32_t* step, const float* state, float* backup, int64_t n, void* zero, int64_t zero_words,
-                                      void* stream) {
-    OTVAE_REQUIRE(step && (n == 0 || (state && backup)) && n >= 0, "otvae_step_begin_slots: bad argument");
-    OTVAE_REQUIRE(zero_words >= 0 && (zero_words == 0 || (zero && ((uintptr_t)zero & 15) == 0 && zero_words % 2 == 0)),
-                  "otvae_step_begin_slots: the range to zero must be 16-byte aligned, an even number of int64 words");
-    const int64_t work = n > zero_words / 2 ? n : zero_words / 2;
-    step_begin_slots_kernel<<<imax(1, imin(cdiv(work, 1024), 1024)), 256, 0, (hipStream_t)stream>>>(step, state, backup, n, (int4*)zero,
-                                                                                                    zero_words / 2);
-    OTVAE_CHECK_LAUNCH("otvae_step_begin_slots");
     return OTVAE_OK;
 }
 

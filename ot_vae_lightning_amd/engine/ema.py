@@ -9,7 +9,7 @@ validation / test / predict epoch.  This class restates that package's published
     num_updates += 1;  d = min(decay, (1 + num_updates) / (10 + num_updates));  shadow -= (1 - d) * (shadow - param)
 
 on the MI355X: with ``engine.HipTrainer`` the update is part of the optimizer kernel's own pass over the flat parameter buffer
-(``otvae_adam_step_ema``: no launch of its own, one update per accepted step, so ``num_updates`` is the device step counter);
+(``otvae_adam_step``: no launch of its own, one update per accepted step, so ``num_updates`` is the device step counter);
 on the host-driven route (the reference's loop with a stock optimizer) ``update()`` is one launch per parameter tensor -- or one in
 all when the parameters are views of one flat buffer (``GraphedNelbo``'s engine).  ``store / copy_to / restore`` are plain copies.
 """

@@ -123,7 +123,7 @@ class HipTrainer:
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps], device=dev, dtype=torch.float32)
         self.step_count = torch.zeros(1, device=dev, dtype=torch.int32)
         # the reference's `ema_decay` (model/base.py:99,146-190): the moving average of the parameters is updated by the optimizer
-        # kernel itself (otvae_adam_step_ema); the model's epoch hooks swap it in and out around evaluation (engine/ema.py)
+        # kernel itself (otvae_adam_step); the model's epoch hooks swap it in and out around evaluation (engine/ema.py)
         self.ema = None
         if getattr(model, "ema_decay", None) is not None and not weak_model:
             self.ema = ParamEMA(self.params, model.ema_decay, flat=self.pflat, in_optimizer=True, step_tensor=self.step_count)
@@ -284,9 +284,9 @@ class HipTrainer:
         # slots (functional.SlotArena)
         z = HF.SlotArena.begin_step(self.device, fused_zero=True)
         guarded = self.step_guard is not None and self.rflat is not None
-        check(self.lib.otvae_step_begin_slots(ptr(self.step_count), ptr(self.rflat) if guarded else None,
-                                              ptr(self.rbackup) if guarded else None, self.rflat.numel() if guarded else 0,
-                                              ptr(z), z.numel() if z is not None else 0, stream()), "otvae_step_begin_slots")
+        check(self.lib.otvae_step_begin(ptr(self.step_count), ptr(self.rflat) if guarded else None,
+                                        ptr(self.rbackup) if guarded else None, self.rflat.numel() if guarded else 0,
+                                        ptr(z), z.numel() if z is not None else 0, stream()), "otvae_step_begin")
 
     @contextmanager
     def _step_scope(self):
@@ -461,12 +461,12 @@ class HipTrainer:
         state = self.rflat if guarded else None  # (None as well when the model has no running state)
         # [total, recon, prior] of this step (static inside a captured step)
         self._watch = watch = getattr(self.model, "_last_out3", None) if guarded else None
-        check(lib.otvae_adam_step_ema(ptr(self.pflat), ptr(self.gflat), ptr(self.m), ptr(self.v), self.pflat.numel(),
-                                      ptr(self.hyper), ptr(self.step_count), self.reducer.grad_scale,
-                                      ptr(self.clip_out) if norm else None, ptr(watch), ptr(self.guard) if guarded else None,
-                                      ptr(state), None if state is None else ptr(self.rbackup), 0 if state is None else state.numel(),
-                                      None if ema is None else ptr(ema.shadow), 0.0 if ema is None else ema.decay, stream()),
-              "otvae_adam_step_ema")
+        check(lib.otvae_adam_step(ptr(self.pflat), ptr(self.gflat), ptr(self.m), ptr(self.v), self.pflat.numel(),
+                                  ptr(self.hyper), ptr(self.step_count), self.reducer.grad_scale,
+                                  ptr(self.clip_out) if norm else None, ptr(watch), ptr(self.guard) if guarded else None,
+                                  ptr(state), None if state is None else ptr(self.rbackup), 0 if state is None else state.numel(),
+                                  None if ema is None else ptr(ema.shadow), 0.0 if ema is None else ema.decay, stream()),
+              "otvae_adam_step")
 
     @property
     def skipped_steps(self) -> int:

@@ -1074,10 +1074,15 @@ def dropout2d(x: Tensor, p: float, key: Tensor, stream_id: int = 0, return_used:
     return (y, used) if return_used else y
 
 
-def dropout2d_mask(used: Tensor, n: int, c: int, p: float) -> Tensor:
-    keep = torch.empty((n, c), device=used.device, dtype=torch.uint8)
-    check(_lib.load().otvae_dropout2d_mask(n, c, float(p), ptr(used), ptr(keep), stream()), "otvae_dropout2d_mask")
+def _keep_mask(used: Tensor, rows: int, cols: int, p: float) -> Tensor:
+    """bool [rows, cols]: what the hashed dropout of the call that left ``used`` keeps; (row, col) as the producing kernel hashes them"""
+    keep = torch.empty((rows, cols), device=used.device, dtype=torch.uint8)
+    check(_lib.load().otvae_dropout_keep_mask(rows, cols, float(p), ptr(used), ptr(keep), stream()), "otvae_dropout_keep_mask")
     return keep.bool()
+
+
+def dropout2d_mask(used: Tensor, n: int, c: int, p: float) -> Tensor:
+    return _keep_mask(used, n, c, p)
 
 
 class _ScaleFn(torch.autograd.Function):
@@ -1519,8 +1524,11 @@ def new_linear_weight(d_out: int, d_in: int, device=None) -> Tensor:
 
 
 class _LayerNormFn(torch.autograd.Function):
+    """y = LayerNorm(x + res), or with ``key`` LayerNorm(res + dropout(x)) in one kernel: the mask is a hash the backward kernel
+    recomputes from the call key the forward left in ``used`` (``None`` without dropout)"""
+
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps):
+    def forward(ctx, x, res, gamma, beta, eps, p, key, stream_id):
         lib = _lib.load()
         d = x.shape[-1]
         m = x.numel() // d
@@ -1530,50 +1538,15 @@ class _LayerNormFn(torch.autograd.Function):
         s = torch.empty_like(x2) if r2 is not None else None
         mean = torch.empty(m, device=x.device, dtype=torch.float32)
         rstd = torch.empty(m, device=x.device, dtype=torch.float32)
-        check(lib.otvae_layernorm_fwd(ptr(x2), ptr(r2), ptr(gamma), ptr(beta), m, d, float(eps), ptr(s), ptr(y), ptr(mean),
-                                      ptr(rstd), stream()), "otvae_layernorm_fwd")
-        ctx.save_for_backward(s if s is not None else x2, gamma, mean, rstd)
+        used = torch.empty(1, device=x.device, dtype=torch.int64) if key is not None else None
+        check(lib.otvae_layernorm_fwd(ptr(x2), ptr(r2), ptr(gamma), ptr(beta), m, d, float(eps), float(p), ptr(key), int(stream_id),
+                                      ptr(s), ptr(y), ptr(mean), ptr(rstd), ptr(used), stream()), "otvae_layernorm_fwd")
+        ctx.save_for_backward(s if s is not None else x2, gamma, mean, rstd, used)
         ctx.has_res = res is not None
         ctx.pref = (gamma, beta)   # the parameters themselves: a trainer's flat-buffer slots hang on them (_grad_buffer)
-        return y.reshape(x.shape)
-
-    @staticmethod
-    def backward(ctx, gy):
-        lib = _lib.load()
-        xs, gamma, mean, rstd = ctx.saved_tensors
-        m, d = xs.shape
-        g2 = gy.reshape(m, d).contiguous()
-        gx = torch.empty_like(xs)
-        # written straight into the trainer's gradient slots when the parameters have them (one copy launch per parameter saved:
-        # 28 per step of the reference's ViT); a parameter normalising twice in one step would need accumulation: not on this path
-        dgamma, dbeta = _grad_buffer(ctx.pref[0], gamma), _grad_buffer(ctx.pref[1], gamma)
-        ws = torch.empty(lib.otvae_layernorm_bwd_ws(m, d), device=xs.device, dtype=torch.float32)
-        check(lib.otvae_layernorm_bwd(ptr(xs), ptr(g2), ptr(gamma), ptr(mean), ptr(rstd), m, d, ptr(gx), ptr(dgamma), ptr(dbeta),
-                                      ptr(ws), stream()), "otvae_layernorm_bwd")
-        gx = gx.reshape(gy.shape)
-        return gx, (gx if ctx.has_res else None), dgamma, dbeta, None
-
-
-class _LayerNormDropoutFn(torch.autograd.Function):
-    """y = LayerNorm(res + dropout(x)) in one kernel; the mask is a hash the backward kernel recomputes"""
-
-    @staticmethod
-    def forward(ctx, x, res, gamma, beta, eps, p, key, stream_id):
-        lib = _lib.load()
-        d = x.shape[-1]
-        m = x.numel() // d
-        x2, r2 = x.reshape(m, d).contiguous(), res.reshape(m, d).contiguous()
-        y, s = torch.empty_like(x2), torch.empty_like(x2)
-        mean = torch.empty(m, device=x.device, dtype=torch.float32)
-        rstd = torch.empty(m, device=x.device, dtype=torch.float32)
-        used = torch.empty(1, device=x.device, dtype=torch.int64)
-        check(lib.otvae_layernorm_dropout_fwd(ptr(x2), ptr(r2), ptr(gamma), ptr(beta), m, d, float(eps), float(p), ptr(key),
-                                              int(stream_id), ptr(s), ptr(y), ptr(mean), ptr(rstd), ptr(used), stream()),
-              "otvae_layernorm_dropout_fwd")
-        ctx.save_for_backward(s, gamma, mean, rstd, used)
-        ctx.pref = (gamma, beta)
         ctx.p = float(p)
-        ctx.mark_non_differentiable(used)
+        if used is not None:
+            ctx.mark_non_differentiable(used)
         return y.reshape(x.shape), used
 
     @staticmethod
@@ -1582,20 +1555,21 @@ class _LayerNormDropoutFn(torch.autograd.Function):
         xs, gamma, mean, rstd, used = ctx.saved_tensors
         m, d = xs.shape
         g2 = gy.reshape(m, d).contiguous()
-        gres, gx = torch.empty_like(xs), torch.empty_like(xs)
+        gx = torch.empty_like(xs)                                       # dL/d(summed row): the residual's gradient
+        gxd = torch.empty_like(xs) if used is not None else None        # gx o keep / (1-p): the thinned operand's
+        # written straight into the trainer's gradient slots when the parameters have them (one copy launch per parameter saved:
+        # 28 per step of the reference's ViT); a parameter normalising twice in one step would need accumulation: not on this path
         dgamma, dbeta = _grad_buffer(ctx.pref[0], gamma), _grad_buffer(ctx.pref[1], gamma)
         ws = torch.empty(lib.otvae_layernorm_bwd_ws(m, d), device=xs.device, dtype=torch.float32)
-        check(lib.otvae_layernorm_dropout_bwd(ptr(xs), ptr(g2), ptr(gamma), ptr(mean), ptr(rstd), m, d, ctx.p, ptr(used), ptr(gres),
-                                              ptr(gx), ptr(dgamma), ptr(dbeta), ptr(ws), stream()), "otvae_layernorm_dropout_bwd")
-        return gx.reshape(gy.shape), gres.reshape(gy.shape), dgamma, dbeta, None, None, None, None
+        check(lib.otvae_layernorm_bwd(ptr(xs), ptr(g2), ptr(gamma), ptr(mean), ptr(rstd), m, d, ctx.p, ptr(used), ptr(gx), ptr(gxd),
+                                      ptr(dgamma), ptr(dbeta), ptr(ws), stream()), "otvae_layernorm_bwd")
+        gx = gx.reshape(gy.shape)
+        return (gxd.reshape(gy.shape) if used is not None else gx), (gx if ctx.has_res else None), dgamma, dbeta, None, None, None, None
 
 
 def layer_norm_dropout_mask(used: Tensor, m: int, d: int, p: float) -> Tensor:
     """the keep mask [M, D] (bool) of the ``layer_norm_tokens(dropout_p > 0)`` call that returned ``used`` -- for tests"""
-    lib = _lib.load()
-    keep = torch.empty((m, d), device=used.device, dtype=torch.uint8)
-    check(lib.otvae_layernorm_dropout_mask(m, d, float(p), ptr(used), ptr(keep), stream()), "otvae_layernorm_dropout_mask")
-    return keep.bool()
+    return _keep_mask(used, m, d, p)
 
 
 def layer_norm_tokens(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5, residual: Optional[Tensor] = None,
@@ -1611,9 +1585,9 @@ def layer_norm_tokens(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5,
     if dropout_p > 0:
         if residual is None or dropout_key is None:
             raise ValueError("`dropout_p` > 0 needs the `residual` the thinned `x` is added to, and a `dropout_key`")
-        y, used = _LayerNormDropoutFn.apply(x, residual, gamma, beta, eps, dropout_p, dropout_key, stream_id)
+        y, used = _LayerNormFn.apply(x, residual, gamma, beta, eps, dropout_p, dropout_key, stream_id)
         return (y, used) if return_used else y
-    return _LayerNormFn.apply(x, residual, gamma, beta, eps)
+    return _LayerNormFn.apply(x, residual, gamma, beta, eps, 0.0, None, 0)[0]
 
 
 class _EmbeddingFn(torch.autograd.Function):
@@ -1785,9 +1759,7 @@ class _CrossAttentionFn(torch.autograd.Function):
 
 def attention_cross_mask(used: Tensor, n: int, tq: int, tk: int, heads: int, p: float) -> Tensor:
     """the keep mask [N, H, Tq, Tk] (bool) of the cross-attention call whose forward left ``used`` -- for tests"""
-    keep = torch.empty((n, heads, tq, tk), device=used.device, dtype=torch.uint8)
-    check(_lib.load().otvae_attn_cross_mask(n, tq, tk, heads, float(p), ptr(used), ptr(keep), stream()), "otvae_attn_cross_mask")
-    return keep.bool()
+    return _keep_mask(used, n * heads * tq, tk, p).reshape(n, heads, tq, tk)
 
 
 def cross_attention_tokens(x: Tensor, memory: Tensor, in_proj_weight: Tensor, in_proj_bias: Optional[Tensor], n_heads: int,
@@ -1815,10 +1787,7 @@ def new_dropout_key(device, seed: Optional[int] = None) -> Tensor:
 
 def attention_dropout_mask(used: Tensor, n: int, t: int, heads: int, p: float) -> Tensor:
     """the keep mask [N, H, T, T] (bool) of the call whose forward returned ``used`` -- for tests"""
-    lib = _lib.load()
-    keep = torch.empty((n, heads, t, t), device=used.device, dtype=torch.uint8)
-    check(lib.otvae_attn_dropout_mask(n, t, heads, float(p), ptr(used), ptr(keep), stream()), "otvae_attn_dropout_mask")
-    return keep.bool()
+    return _keep_mask(used, n * heads * t, t, p).reshape(n, heads, t, t)
 
 
 def mha_attention_tokens(qkv: Tensor, n_heads: int, dropout_p: float = 0.0, dropout_key: Optional[Tensor] = None,

@@ -63,7 +63,7 @@ def test_library_exports_every_declared_symbol(lib_path):
     for name in sorted(_header_functions()):
         assert hasattr(lib, name), f"{name} declared in include/otvae.h but not exported"
     lib.otvae_abi_version.restype = ctypes.c_int
-    assert lib.otvae_abi_version() == 1
+    assert lib.otvae_abi_version() == 2
 
 
 def test_library_contains_gfx950_code_object(lib_path):

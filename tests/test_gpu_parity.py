@@ -2503,7 +2503,7 @@ def test_conditional_vit_vae_nelbo_vs_reference_golden(A):
 def test_attention_with_dropout_matches_reference_given_its_own_mask(n, t, heads, c, p, causal):
     """``otvae_attn_dropout_fwd/_bwd`` (nn.MultiheadAttention's dropout on the attention probabilities, reference
     networks/vit.py:157-172 in training mode) against plain torch arithmetic that is handed the kernel's own keep mask
-    (``otvae_attn_dropout_mask``): out = (softmax(q k^T / sqrt(C)) o keep / (1-p)) v and all three input gradients."""
+    (``otvae_dropout_keep_mask``): out = (softmax(q k^T / sqrt(C)) o keep / (1-p)) v and all three input gradients."""
     import ot_vae_lightning_amd.functional as HF
     rep = Report(f"attention with dropout N={n} T={t} H={heads} C={c} p={p} causal={causal}")
     qkv = normal((n, t, 3 * heads * c), 700 + t).cuda().requires_grad_(True)
@@ -2569,7 +2569,7 @@ def test_attention_dropout_zero_probability_is_the_plain_kernel_and_bad_argument
 
 @pytest.mark.parametrize("m,d,p", [(1235, 256, 0.1), (77, 32, 0.5), (300, 100, 0.25), (64, 1000, 0.1)])
 def test_layernorm_with_fused_dropout_matches_reference_given_its_own_mask(m, d, p):
-    """``otvae_layernorm_dropout_fwd/_bwd``: y = LayerNorm(res + dropout(x)), the post-norm block of a training-mode
+    """``otvae_layernorm_fwd/_bwd`` with a dropout key: y = LayerNorm(res + dropout(x)), the post-norm block of a training-mode
     nn.TransformerEncoderLayer (reference networks/vit.py:157-172), against torch arithmetic handed the kernel's mask."""
     import ot_vae_lightning_amd.functional as HF
     rep = Report(f"LayerNorm(res + dropout(x)) M={m} D={d} p={p}")
