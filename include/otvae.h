@@ -390,6 +390,19 @@ int otvae_film_fwd(const float* x, const float* scale, const float* bias, int N,
 /* gx = g * scale; gscale[n][c] = sum_hw g x; gbias[n][c] = sum_hw g */
 int otvae_film_bwd(const float* g, const float* x, const float* scale, int N, int HW, int C, float* gx, float* gscale, float* gbias,
                    void* stream);
+/* FiLM and the layer's activation in one pass each way (csrc/film_act.hip): out = act(x * scale[n][c] + bias[n][c]), act_kind as in
+ * otvae_bn_act_fwd (0: none); the same bits as otvae_film_fwd followed by otvae_bn_act_fwd.  N <= 65535, HW * C < 2^31. */
+int otvae_film_act_fwd(const float* x, const float* scale, const float* bias, int N, int HW, int C, int act_kind, float* out,
+                       void* stream);
+/* v = x * scale + bias; ga = g * act'(v); gx = ga * scale; gscale[n][c] = sum_hw ga x; gbias[n][c] = sum_hw ga (fp64 sums in a fixed
+ * order: bit-reproducible).  gscale / gbias NULL together: only gx.  ws: otvae_film_act_bwd_ws bytes, 8-byte aligned (NULL when that
+ * is 0 or gscale is NULL): fp64 partials of the row chunks a small batch is cut into. */
+int64_t otvae_film_act_bwd_ws(int N, int HW, int C);
+int otvae_film_act_bwd(const float* g, const float* x, const float* scale, const float* bias, int N, int HW, int C, int act_kind,
+                       float* gx, float* gscale, float* gbias, void* ws, void* stream);
+/* Gaussian Fourier features of GaussianFourierProjection (networks/nets_utils.py:51-52): out[n] = [sin(p), cos(p)] [N][2 * half],
+ * p = ((t[n] * w[j]) * 2) * pi in fp32 in that order; t [N], w [half] */
+int otvae_fourier_features(const float* t, const float* w, int N, int half, float* out, void* stream);
 /* nn.Dropout2d(p): y = keep(n, c) ? x / (1 - p) : 0 with keep = hash(call key, n, c); key = device int64[2] {seed, call counter},
  * used[0] <- the call key (the backward recomputes the mask from it; no mask tensor) */
 int otvae_dropout2d_fwd(const float* x, int N, int HW, int C, float p, const int64_t* key, int stream_id, float* y, int64_t* used,

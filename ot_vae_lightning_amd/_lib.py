@@ -117,6 +117,10 @@ SIGNATURES = {
     "otvae_embedding_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "otvae_film_fwd": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "otvae_film_bwd": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "otvae_film_act_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+    "otvae_film_act_bwd_ws": (i64, [i32, i32, i32]),
+    "otvae_film_act_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "otvae_fourier_features": (i32, [vp, vp, i32, i32, vp, vp]),
     "otvae_dropout2d_fwd": (i32, [vp, i32, i32, i32, f32, vp, i32, vp, vp, vp]),
     "otvae_dropout2d_bwd": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
     "otvae_mvn_logprob_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),

@@ -1041,6 +1041,63 @@ class _FilmFn(torch.autograd.Function):
         return gx, gs, gb
 
 
+class _FilmActFn(torch.autograd.Function):
+    """act(x * scale[n, c] + bias[n, c]): FiLM conditioning and the layer's activation as ONE launch each way (csrc/film_act.hip) --
+    what ``_FilmFn`` + ``_BnActFn(kind)`` compute in two, bit for bit in the forward pass.  ``scale`` / ``bias`` that take no gradient
+    (an embedding computed under ``no_grad``) skip the per-sample sums."""
+
+    @staticmethod
+    def forward(ctx, x, scale, bias, kind):
+        n, c, h, w = x.shape
+        out = empty_nhwc(n, c, h, w, x)
+        scale, bias = scale.contiguous(), bias.contiguous()
+        check(_lib.load().otvae_film_act_fwd(ptr(x), ptr(scale), ptr(bias), n, h * w, c, kind, ptr(out), stream()), "otvae_film_act_fwd")
+        ctx.kind = kind
+        ctx.save_for_backward(x, scale, bias)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, scale, bias = ctx.saved_tensors
+        n, c, h, w = x.shape
+        g = as_nhwc(g)
+        gx = empty_nhwc(n, c, h, w, x)
+        gs = gb = ws = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gs, gb = torch.empty_like(scale), torch.empty_like(scale)
+            nbytes = lib.otvae_film_act_bwd_ws(n, h * w, c)
+            if nbytes:
+                ws = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+        check(lib.otvae_film_act_bwd(ptr(g), ptr(x), ptr(scale), ptr(bias), n, h * w, c, ctx.kind, ptr(gx), ptr(gs), ptr(gb), ptr(ws),
+                                     stream()), "otvae_film_act_bwd")
+        return gx, gs, gb, None
+
+
+def film_act(x: Tensor, scale: Tensor, bias: Tensor, kind: int = 0) -> Tensor:
+    """``act(x * scale[:, :, None, None] + bias[:, :, None, None])`` on a [N, C, H, W] map (made channels-last if it is not), ``kind``
+    an ``ACT_KINDS`` value; differentiable in all three tensors."""
+    _lib.require_cuda(x, "film_act input")
+    if scale.shape != (x.shape[0], x.shape[1]) or bias.shape != scale.shape:
+        raise ValueError(f"film_act: scale / bias must be [N, C] = {(x.shape[0], x.shape[1])}, got {tuple(scale.shape)} / {tuple(bias.shape)}")
+    if int(kind) not in ACT_KINDS.values():
+        raise ValueError(f"film_act: unknown activation kind {kind}")
+    return _FilmActFn.apply(as_nhwc(x), scale, bias, int(kind))
+
+
+def fourier_features(t: Tensor, weight: Tensor) -> Tensor:
+    """[sin(p), cos(p)] [N, 2 * half] with p = ((t[n] * weight[j]) * 2) * pi evaluated in fp32 in that order (the reference's
+    ``input.unsqueeze(-1) * self.weight * 2 * np.pi``, nets_utils.py:51-52); t [N], weight [half] or [1, half].  Forward only."""
+    _lib.require_cuda(t, "fourier_features input")
+    if t.dim() != 1:
+        raise ValueError("`t` is expected to be 1-dimensional")
+    t = t.detach().float().contiguous()
+    w = weight.detach().float().reshape(-1).contiguous()
+    out = torch.empty((t.shape[0], 2 * w.shape[0]), device=t.device, dtype=torch.float32)
+    check(_lib.load().otvae_fourier_features(ptr(t), ptr(w), t.shape[0], w.shape[0], ptr(out), stream()), "otvae_fourier_features")
+    return out
+
+
 class _Dropout2dFn(torch.autograd.Function):
     """nn.Dropout2d(p) in training mode: whole (sample, channel) maps dropped; mask recomputed from the call key in backward"""
 
@@ -1194,9 +1251,7 @@ def _conv_layer_general(x: Tensor, br: dict, training: bool) -> Tensor:
     elif has_norm or norm_kind != 0:
         a = _BnActFn.apply(x, br.get("gamma"), br.get("beta"), stats, norm_kind, (br.get("gamma"), br.get("beta")))
     if film is not None:
-        a = _FilmFn.apply(a, film[0], film[1])
-        if kind != 0:
-            a = _BnActFn.apply(a, None, None, None, kind, (None, None))
+        a = _FilmActFn.apply(as_nhwc(a), film[0], film[1], kind)
     up_module, down_module = br.get("up_module"), br.get("down_module")
     if up_module is not None:   # a user-supplied module between the activation and the convolution (cnn.py:187)
         a = as_nhwc(up_module(a))

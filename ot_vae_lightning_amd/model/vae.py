@@ -109,7 +109,7 @@ class VAE(VisionModule):
         samples, target, kwargs = batch["samples"], batch["target"], batch["kwargs"]
         batch_size = samples.size(0)
         latents, prior_loss, prior_artifacts = self.encode(samples, expand=True, return_prior_artifacts=True, **kwargs)
-        prior_loss = self.per_sample_prior_loss(prior_loss, prior_artifacts)
+        prior_loss = self.per_sample_prior_loss(prior_loss, prior_artifacts, **kwargs)
         reconstructions = self.decode(latents, expand_kwargs=True, **kwargs)
         reconstructions_mean = self._reduce_mean(reconstructions)
         out3 = HF.nelbo_loss(reconstructions_mean, target, prior_loss)   # [total, recon, prior/(C*H*W)]

@@ -9,9 +9,9 @@ stay channels-last between layers, and attention never materialises the TxT matr
 
 Activations other than ReLU (LeakyReLU(0.2), SELU, GELU, SiLU) and ``equalized_lr`` -- what the reference's
 configs/vae/defaults_imagenet.yaml trains with -- run unfused around the same kernels (functional._conv_layer_general,
-csrc/activation.hip), and so do GroupNorm / InstanceNorm2d (csrc/groupnorm.hip), FiLM conditioning (`additional_embed`) and
-Dropout2d (csrc/film_dropout2d.hip).  Grouped and dilated layers keep nn.Conv2d's parameter shape and expand it per call into the
-dense weight the kernels take (csrc/weight_expand.hip: zeros between groups and in the holes of the dilation; up to 7 x 7 taps).
+csrc/activation.hip), and so do GroupNorm / InstanceNorm2d (csrc/groupnorm.hip), FiLM conditioning (`additional_embed`: one launch
+with the activation, csrc/film_act.hip) and Dropout2d (csrc/film_dropout2d.hip).  Grouped and dilated layers keep nn.Conv2d's
+parameter shape and expand it per call into the dense weight the kernels take (csrc/weight_expand.hip: zeros between groups and in the holes of the dilation; up to 7 x 7 taps).
 A module-valued ``up_sample`` / ``down_sample`` (the user's own plug-in) is called as given, around the layer's kernels.
 """
 import math
@@ -24,7 +24,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import functional as HF
-from .nets_utils import FilterSequential, QKVAttention
+from .nets_utils import FilterSequential, GaussianFourierProjection, QKVAttention
 
 __all__ = ["ConvLayer", "Conv1x1", "ConvBlock", "AttentionBlock", "CNN", "AutoEncoder"]
 
@@ -363,7 +363,8 @@ class CNN(FilterSequential):
 
 class AutoEncoder(nn.Module):
     """encoder CNN + mirrored decoder CNN with ``encode``/``decode``/``latent_size`` (reference cnn.py:463-600).
-    Class/time conditioning feeds FiLM embeddings, which the MI355X ConvLayer applies through ``_film``."""
+    ``num_classes`` / ``time_embed_dim`` add a class ``nn.Embedding`` and a ``GaussianFourierProjection`` of the time; their
+    concatenation is the FiLM embedding of every ConvLayer of both networks (``ConvLayer._film`` -> functional._FilmActFn)."""
 
     def __init__(self, in_features: int, latent_features: int, in_resolution: Optional[int] = None,
                  latent_resolution: Optional[int] = None, intermediate_features: Optional[List[int]] = None,
@@ -374,26 +375,43 @@ class AutoEncoder(nn.Module):
                  equalized_lr: Optional[float] = None, dropout: float = 0., kernel_size=3, stride=1, padding=1,
                  dilation=1, groups: int = 1, bias: bool = True) -> None:
         super().__init__()
-        if bool(num_classes) or bool(time_embed_dim):
-            raise NotImplementedError("class / time conditioned AutoEncoder is not supported on the MI355X path")
         enc_out = latent_features * (1 + int(double_encoded_features))
         self.latent_size = torch.Size([enc_out, latent_resolution, latent_resolution])
-        self.class_embed = None
-        self.time_embed = None
+        # the reference's creation order (cnn.py:540-561): class_embed, time_embed, encoder, decoder -- same draws under a shared seed,
+        # same order of the state dict
+        cls_embed = 2 ** (int(math.log10(num_classes)) + 5) if bool(num_classes) else None
+        self.class_embed = nn.Embedding(num_classes, cls_embed) if bool(num_classes) else None
+        self.time_embed = GaussianFourierProjection(time_embed_dim, time_embed_dim) if bool(time_embed_dim) else None
+        additional_embed = (cls_embed or 0) + (time_embed_dim or 0) or None   # the sum of the widths that are present
         self.encoder = CNN(in_features, enc_out, in_resolution, latent_resolution, intermediate_features, capacity,
-                           max_attn_res, n_layers, residual, down_up_sample, False, None, normalization, activation,
+                           max_attn_res, n_layers, residual, down_up_sample, False, additional_embed, normalization, activation,
                            equalized_lr, dropout, kernel_size, stride, padding, dilation, groups, bias)
         self.decoder = CNN(latent_features, in_features, latent_resolution, in_resolution,
                            intermediate_features[::-1] if intermediate_features is not None else None, capacity,
-                           max_attn_res, n_layers, residual, False, down_up_sample, None, normalization, activation,
+                           max_attn_res, n_layers, residual, False, down_up_sample, additional_embed, normalization, activation,
                            equalized_lr, dropout, kernel_size, stride, padding, dilation, groups, bias)
 
     def embed(self, labels: Optional[Tensor] = None, time: Optional[Tensor] = None):
-        if labels is not None:
-            warnings.warn("given conditional argument `labels` but `self.class_embed` is None.")
-        if time is not None:
-            warnings.warn("given conditional argument `time` but `self.time_embed` is None.")
-        return None
+        """The FiLM embedding [N, cls_embed + time_embed_dim] every ConvLayer projects (reference cnn.py:563-591): the class
+        embedding, the time embedding, both concatenated in that order, or None for an unconditioned network."""
+        class_embed, time_embed = None, None
+        if labels is not None and self.class_embed is None:
+            warnings.warn("given conditional argument `labels` but `self.class_embed` is None. "
+                          "To enable class-conditioned CNNs, use `ae = AutoEncoder(num_classes=...)`.")
+        if self.class_embed is not None and labels is None:
+            raise ValueError("`num_classes` specified but `labels` is None. Can't infer the class embedding.")
+        if self.class_embed is not None:
+            class_embed = self.class_embed(labels)
+        if time is not None and self.time_embed is None:
+            warnings.warn("given conditional argument `time` but `self.time_embed` is None. "
+                          "To enable time-conditioned CNNs, use `ae = AutoEncoder(time_embed_dim=...)`.")
+        if self.time_embed is not None and time is None:
+            raise ValueError("`time_embed_dim` specified but `time` is None. Can't infer the time embedding.")
+        if self.time_embed is not None:
+            time_embed = self.time_embed(time)
+        if class_embed is not None and time_embed is not None:
+            return torch.cat([class_embed, time_embed], dim=1)
+        return class_embed if class_embed is not None else time_embed
 
     def encode(self, x: Tensor, labels: Optional[Tensor] = None, time: Optional[Tensor] = None) -> Tensor:
         return self.encoder(x, self.embed(labels, time))
