@@ -196,6 +196,13 @@ int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream);
  * bit i of packed_mask: job i ran inside one packed conv_jobs_kernel launch; uniform_tap: that launch's template flavour
  * (1 = conv_jobs_kernel<true>), -1 if nothing was packed. */
 int otvae_conv_multi_last(unsigned* packed_mask, int* uniform_tap);
+/* Host query, launches nothing: the (tile, tap) visits of the implicit-GEMM launch that serves the forward pass (mode 0) or the data
+ * gradient (mode 1) of a layer -- `launch_rule`: every 64-row tile walks each tap some row of the launch can use (the rule before
+ * the per-tile list, and of OTVAE_GEMM_LIVE_TAPS=0); `per_tile`: rows position-major, a tile walks the taps one of ITS rows can use.
+ * Both counts are equal for a layer on the scalar path (a channel count not a multiple of 4).  The counts assume 16-byte aligned
+ * tensors: a launch given a misaligned x / gy, weight, scale or shift pointer takes the scalar path whatever its channel counts.  Returns OTVAE_EUNSUPPORTED when the
+ * image-tile or direct kernels take the layer (not served by the implicit GEMM). */
+int otvae_conv_gemm_chunks(const otvae_conv_geom* g, int mode, int64_t* launch_rule, int64_t* per_tile);
 
 /* ---- QKVAttention (networks/nets_utils.py:63-82) ---------------------------------------------------------- */
 /* qkv [N][T][3*H*C] (channel = which*H*C + h*C + c) -> out [N][T][H*C]; lse [N][H][T] saved for backward.

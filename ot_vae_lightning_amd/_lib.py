@@ -20,6 +20,7 @@ vp, i32, i64, f32, f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 pp = C.POINTER(C.c_void_p)  # host array of device pointers
 pi32 = C.POINTER(C.c_int)
 pu32 = C.POINTER(C.c_uint32)
+pi64 = C.POINTER(C.c_int64)
 
 
 class ConvGeom(C.Structure):
@@ -78,6 +79,7 @@ SIGNATURES = {
     "otvae_gmm_diag_energy": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "otvae_conv_multi": (i32, [i32, pj, vp]),
     "otvae_conv_multi_last": (i32, [pu32, pi32]),
+    "otvae_conv_gemm_chunks": (i32, [pg, i32, pi64, pi64]),
     "otvae_attn_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "otvae_attn_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "otvae_attn_fwd_scaled": (i32, [vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]),

@@ -14,8 +14,9 @@
 // all loads of the chunk in flight at once, double-buffered against the MFMAs of the previous chunk; each wave then
 // feeds v_mfma_f32_16x16x4_f32 from LDS (A[row = lane&15][k = lane>>4], B[k = lane>>4][col = lane&15],
 // D[r] = D[(lane>>4)*4 + r][lane&15]).  LDS leading dimensions (KC+2 / BN+16) make both operand reads conflict-free.
-// Taps that cannot touch the image for any row of the layer (e.g. 8 of the 9 taps of a 3x3 conv on a 1x1 map) are
-// dropped from K at kernel start.
+// Taps that cannot touch the image for any row of a TILE are dropped from that tile's K (vector paths: the rows are ordered
+// position-major, so a tile holds one or two output positions and e.g. a corner of a 3x3 conv walks 4 of the 9 taps); the
+// scalar path and OTVAE_GEMM_LIVE_TAPS=0 keep the memory row order and drop only the taps no row of the launch can use.
 #include "common.h"
 #include "conv_small.h"  // struct Geom + the direct VALU kernels used when both channel counts are tiny
 #include "conv_tile.h"   // image-tile MFMA convolution (whole images in LDS) for maps up to 16x16
@@ -76,7 +77,7 @@ __device__ __forceinline__ int imin_dev(int a, int b) { return a < b ? a : b; }
 // these decodes sit in per-tile / per-output-element code of kernels that are bound by vector-instruction issue, so
 // they go through fast_div (one multiply) whenever the row count is below 2^22 (exactness bound of fast_div).
 struct RowDiv {
-    float iWo, iHo, iWs, iHs, iW2, iH2;
+    float iWo, iHo, iWs, iHs, iW2, iH2, iN;
     bool small;
 };
 __device__ __forceinline__ RowDiv make_rowdiv(const Geom& g, unsigned rows_max) {
@@ -84,6 +85,7 @@ __device__ __forceinline__ RowDiv make_rowdiv(const Geom& g, unsigned rows_max) 
     r.iWo = 1.0f / (float)g.Wo, r.iHo = 1.0f / (float)g.Ho;
     r.iWs = 1.0f / (float)g.Ws, r.iHs = 1.0f / (float)g.Hs;
     r.iW2 = 1.0f / (float)imax_dev(g.Ws >> 1, 1), r.iH2 = 1.0f / (float)imax_dev(g.Hs >> 1, 1);
+    r.iN = 1.0f / (float)g.N;
     r.small = rows_max < (1u << 22);
     return r;
 }
@@ -91,30 +93,59 @@ __device__ __forceinline__ unsigned rdiv(unsigned k, unsigned d, float inv_d, bo
     return small ? (unsigned)fast_div((int)k, inv_d) : k / d;
 }
 
-__device__ __forceinline__ void dgrad_row_to_pos(const Geom& g, const RowDiv& rd, unsigned row, int py, int px, int& n, int& iy,
-                                                 int& ix) {
-    if (g.up == 2) {
-        const unsigned parent = row >> 2, child = row & 3;
-        const unsigned t = rdiv(parent, g.Ws, rd.iWs, rd.small);
-        const int sx = parent - t * g.Ws;
-        n = rdiv(t, g.Hs, rd.iHs, rd.small);
-        const int sy = t - (unsigned)n * g.Hs;
+// q -> (image, y, x) on a map of width W (and height H).  Memory order: q = (n*H + y)*W + x.  Position-major (pm, the order of the
+// vector paths): q = (y*W + x)*N + n, the image index runs fastest, so the 64 rows of a tile share one (y, x) -- two when N is ragged.
+__device__ __forceinline__ void row_decode(const Geom& g, const RowDiv& rd, bool pm, unsigned q, unsigned W, float iW, unsigned H,
+                                           float iH, int& n, int& y, int& x) {
+    if (pm) {
+        const unsigned pos = rdiv(q, g.N, rd.iN, rd.small);
+        n = q - pos * g.N;
+        y = rdiv(pos, W, iW, rd.small);
+        x = pos - (unsigned)y * W;
+    } else {
+        const unsigned t = rdiv(q, W, iW, rd.small);
+        x = q - t * W;
+        n = rdiv(t, H, iH, rd.small);
+        y = t - (unsigned)n * H;
+    }
+}
+
+__device__ __forceinline__ void dgrad_row_to_pos(const Geom& g, const RowDiv& rd, bool pm, unsigned row, int py, int px, int& n,
+                                                 int& iy, int& ix) {
+    if (g.up == 2) {  // the 4 children of a source pixel stay together (one lane's accumulator registers) in either order
+        const unsigned child = row & 3;
+        int sy, sx;
+        row_decode(g, rd, pm, row >> 2, g.Ws, rd.iWs, g.Hs, rd.iHs, n, sy, sx);
         iy = 2 * sy + (child >> 1);
         ix = 2 * sx + (child & 1);
     } else if (g.stride == 2) {
-        const int W2 = g.Ws >> 1, H2 = g.Hs >> 1;
-        const unsigned t = rdiv(row, W2, rd.iW2, rd.small);
-        const int jx = row - t * W2;
-        n = rdiv(t, H2, rd.iH2, rd.small);
-        const int jy = t - (unsigned)n * H2;
+        int jy, jx;
+        row_decode(g, rd, pm, row, g.Ws >> 1, rd.iW2, g.Hs >> 1, rd.iH2, n, jy, jx);
         iy = 2 * jy + py;
         ix = 2 * jx + px;
     } else {
-        const unsigned t = rdiv(row, g.Ws, rd.iWs, rd.small);
-        ix = row - t * g.Ws;
-        n = rdiv(t, g.Hs, rd.iHs, rd.small);
-        iy = t - (unsigned)n * g.Hs;
+        row_decode(g, rd, pm, row, g.Ws, rd.iWs, g.Hs, rd.iHs, n, iy, ix);
     }
+}
+
+// ---- which taps a row needs: ONE rule for the gather, the per-tile tap list and the host's otvae_conv_gemm_chunks
+// A row is anchored at (ry, rx) = (oy, ox) * stride in the forward pass and (iy, ix) in the data gradient.  Tap (kh, kw) reads the
+// source coordinate (ry + dy, rx + dx) >> sh with (dy, dx) from tap_offset, and has an operand iff that coordinate lies in [0, lim).
+// In the stride-2 data gradient a tap serves only the parity class (py, px) of (iy, ix) in which iy + dy, ix + dx are even.
+__host__ __device__ __forceinline__ void tap_offset(int mode, int pad, int kh, int kw, int& dy, int& dx) {
+    dy = mode == 0 ? kh - pad : pad - kh;
+    dx = mode == 0 ? kw - pad : pad - kw;
+}
+__host__ __device__ __forceinline__ bool tap_in_class(int mode, int stride, int py, int px, int dy, int dx) {
+    return mode == 0 || stride != 2 || ((((py + dy) | (px + dx)) & 1) == 0);
+}
+__host__ __device__ __forceinline__ bool tap_in_range(int ry, int rx, int dy, int dx, int lim_y, int lim_x) {
+    return (unsigned)(ry + dy) < (unsigned)lim_y && (unsigned)(rx + dx) < (unsigned)lim_x;
+}
+// rows of a launch (of one parity class in the stride-2 data gradient)
+__host__ __device__ __forceinline__ unsigned gemm_rows(const Geom& g, int mode) {
+    return mode == 0 ? (unsigned)g.N * g.Ho * g.Wo
+                     : (g.stride == 2 ? (unsigned)g.N * (g.Hs >> 1) * (g.Ws >> 1) : (unsigned)g.N * (g.Hs * g.up) * (g.Ws * g.up));
 }
 
 // LDS layout of one workgroup (carved out of a raw buffer so that the same body can run inside the multi-job kernel)
@@ -132,7 +163,9 @@ struct GemmSmem {
 };
 
 // (bx, by, bz) / (gx, gz): the block's coordinates and the extent of the (virtual) grid of THIS layer
-template <int MODE, int NT, bool VEC, bool UT = false>
+// LIVE (vector paths only): position-major rows and a tap list per tile; otherwise memory row order and one list per launch.  A
+// compile-time flag: as a run-time one it cost conv_jobs_kernel 41 VGPRs and a private copy of its job table.
+template <int MODE, int NT, bool VEC, bool UT = false, bool LIVE = false>
 __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Geom& g, const float* __restrict__ S,
                                                const float* __restrict__ scale, const float* __restrict__ shift, int relu,
                                                const float* __restrict__ Bmat,
@@ -171,31 +204,22 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
     const int lim_y = MODE == 0 ? Hu : g.Ho * g.stride, lim_x = MODE == 0 ? Wu : g.Wo * g.stride;
     const int sh = MODE == 0 ? g.up - 1 : g.stride - 1;
     const int srcH = MODE == 0 ? g.Hs : g.Ho, srcW = MODE == 0 ? g.Ws : g.Wo;
-    const unsigned rows = MODE == 0 ? (unsigned)g.N * g.Ho * g.Wo
-                                    : (g.stride == 2 ? (unsigned)g.N * (g.Hs >> 1) * (g.Ws >> 1) : (unsigned)g.N * Hu * Wu);
+    const unsigned rows = gemm_rows(g, MODE);
     const unsigned ntiles = (rows + TM - 1) / TM;
     const RowDiv rd = make_rowdiv(g, rows);
+    constexpr bool live = VEC && LIVE;
 
-    // ---- valid tap list (uniform over the launch, resp. over the parity class)
-    if (tid == 0) {
+    // ---- launch-wide tap list (uniform over the launch, resp. over the parity class): a tap some row of the layer can use
+    if (!live && tid == 0) {
         int nt = 0;
         for (int kh = 0; kh < g.KH; ++kh)
             for (int kw = 0; kw < g.KW; ++kw) {
-                bool ok;
                 int dy, dx;
-                if (MODE == 0) {
-                    // row anchor = (oy*stride, ox*stride); tap offset = kh - pad
-                    dy = kh - g.pad;
-                    dx = kw - g.pad;
-                    ok = (dy + (g.Ho - 1) * g.stride >= 0) && (dy < Hu) && (dx + (g.Wo - 1) * g.stride >= 0) && (dx < Wu);
-                } else {
-                    // row anchor = (iy, ix); t = iy + pad - kh must be a multiple of stride inside [0, Ho*stride)
-                    dy = g.pad - kh;
-                    dx = g.pad - kw;
-                    ok = true;
-                    if (g.stride == 2) ok = (((py + dy) & 1) == 0) && (((px + dx) & 1) == 0);
-                    ok = ok && (Hu - 1 + dy >= 0) && (dy < lim_y) && (Wu - 1 + dx >= 0) && (dx < lim_x);
-                }
+                tap_offset(MODE, g.pad, kh, kw, dy, dx);
+                // the anchors of a launch span [0, last] in y and in x: some row is in range iff the two intervals meet
+                const int last_y = MODE == 0 ? (g.Ho - 1) * g.stride : Hu - 1, last_x = MODE == 0 ? (g.Wo - 1) * g.stride : Wu - 1;
+                const bool ok = tap_in_class(MODE, g.stride, py, px, dy, dx) && (last_y + dy >= 0) && (dy < lim_y) &&
+                                (last_x + dx >= 0) && (dx < lim_x);
                 if (ok) {
                     tap_dy[nt] = dy;
                     tap_dx[nt] = dx;
@@ -205,10 +229,6 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
             }
         s_ntaps = nt;
     }
-    __syncthreads();
-    const int ntaps = s_ntaps;
-    const int K = ntaps * CK;
-    const int nch = (K + KC - 1) / KC;
     const float inv_ck = 1.0f / (float)CK;
     // UT (host-selected when VEC and CK % KC == 0): the uniform-tap pipeline below replaces the general staging
     const int cpt = CK / KC;  // chunks per tap (ut)
@@ -223,29 +243,48 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
 
     for (unsigned tile = bx; tile < ntiles; tile += gx) {
         __syncthreads();  // readers of row_* / LDS buffers of the previous tile are done
-        if (tid < TM) {
+        if (tid < TM) {  // wave 0: one lane per row
             const unsigned row = tile * TM + tid;
             int n = -1, ry = 0, rx = 0;
             if (row < rows) {
                 if (MODE == 0) {
-                    const unsigned t = rdiv(row, g.Wo, rd.iWo, rd.small);
-                    const int ox = row - t * g.Wo;
-                    n = rdiv(t, g.Ho, rd.iHo, rd.small);
-                    const int oy = t - (unsigned)n * g.Ho;
+                    int oy, ox;
+                    row_decode(g, rd, live, row, g.Wo, rd.iWo, g.Ho, rd.iHo, n, oy, ox);
                     ry = oy * g.stride;
                     rx = ox * g.stride;
                 } else {
-                    int iy, ix;
-                    dgrad_row_to_pos(g, rd, row, py, px, n, iy, ix);
-                    ry = iy;
-                    rx = ix;
+                    dgrad_row_to_pos(g, rd, live, row, py, px, n, ry, rx);
                 }
             }
             row_n[tid] = n;
             row_y[tid] = ry;
             row_x[tid] = rx;
+            if (live) {
+                // ---- this tile's tap list: a tap is kept iff some valid row of the tile has an operand under it -- one test per lane
+                // (row) and a wave-wide OR per candidate, so the count and the offsets stay in scalar registers -- in ascending
+                // (kh, kw) order: every output's k order is the one of the launch-wide list with all-zero taps left out
+                int nt = 0, t = 0;
+                for (int kh = 0; kh < g.KH; ++kh)
+                    for (int kw = 0; kw < g.KW; ++kw, ++t) {
+                        int dy, dx;
+                        tap_offset(MODE, g.pad, kh, kw, dy, dx);
+                        const bool ok = n >= 0 && tap_in_class(MODE, g.stride, py, px, dy, dx) && tap_in_range(ry, rx, dy, dx, lim_y, lim_x);
+                        if (__ballot(ok) != 0ull) {
+                            if (tid == 0) {
+                                tap_dy[nt] = dy;
+                                tap_dx[nt] = dx;
+                                tap_w[nt] = t;
+                            }
+                            ++nt;
+                        }
+                    }
+                if (tid == 0) s_ntaps = nt;
+            }
         }
         __syncthreads();
+        const int ntaps = s_ntaps;
+        const int K = ntaps * CK;
+        const int nch = (K + KC - 1) / KC;
 
         f32x4 acc[NT];
 #pragma unroll
@@ -294,7 +333,7 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                 for (int i = 0; i < 2; ++i) {
                     const int ty = vr_y[i] + dy, tx = vr_x[i] + dx;
                     areg4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (kv && vr_n[i] >= 0 && (unsigned)ty < (unsigned)lim_y && (unsigned)tx < (unsigned)lim_x) {
+                    if (kv && vr_n[i] >= 0 && tap_in_range(vr_y[i], vr_x[i], dy, dx, lim_y, lim_x)) {
                         const unsigned pix = ((unsigned)vr_n[i] * srcH + (ty >> sh)) * srcW + (tx >> sh);
                         areg4[i] = *reinterpret_cast<const float4*>(S + (size_t)pix * CK + c);
                         a_ok |= 1 << i;
@@ -406,7 +445,7 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
         };
 
         if constexpr (VEC && UT) {
-            {
+            if (nch > 0) {  // (no tap at all: a parity class of a 1x1 stride-2 layer)
                 // Uniform-tap pipeline, TWO chunks of operands in flight in registers (set = chunk & 1) on top of the
                 // double-buffered LDS tile.  Measured on a 64->64 3x3 layer at 2x2 (18 chunks, one wave per SIMD):
                 // of 18.3 us, 6 us were the exposed part of the load latency with one chunk in flight.  Every global
@@ -425,7 +464,7 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
 #pragma unroll
                         for (int i = 0; i < 2; ++i) {
                             const int ty = vr_y[i] + dy, tx = vr_x[i] + dx;
-                            const bool valid = vr_n[i] >= 0 && (unsigned)ty < (unsigned)lim_y && (unsigned)tx < (unsigned)lim_x;
+                            const bool valid = vr_n[i] >= 0 && tap_in_range(vr_y[i], vr_x[i], dy, dx, lim_y, lim_x);
                             u_off[i] = valid ? (((unsigned)vr_n[i] * srcH + (ty >> sh)) * srcW + (tx >> sh)) * (unsigned)CK : 0u;
                             u_ok |= (valid ? 1 : 0) << i;
                         }
@@ -546,8 +585,17 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
             }
         }
 
-        // ---- epilogue
-        const unsigned row0 = tile * TM + wave * 16 + kq * 4;
+        // ---- epilogue: the lane's 4 accumulator rows are the tile's rows rl0 .. rl0 + 3; their output pixels (memory order, -1 past
+        // the end) come from the (n, y, x) the tile prologue decoded, whichever order the rows are in
+        const int rl0 = wave * 16 + kq * 4;
+        const int osh = MODE == 0 ? g.stride - 1 : g.up - 1;  // anchor -> output pixel (data gradient with up 2: the source pixel)
+        const int oH = MODE == 0 ? g.Ho : g.Hs, oW = MODE == 0 ? g.Wo : g.Ws;
+        int opix[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = row_n[rl0 + r];
+            opix[r] = n < 0 ? -1 : (n * oH + (row_y[rl0 + r] >> osh)) * oW + (row_x[rl0 + r] >> osh);
+        }
         if (MODE == 0) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
@@ -556,9 +604,8 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                     const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const unsigned pm = row0 + r;
-                        if (pm < rows) {
-                            const size_t o = (size_t)pm * g.Cn + col;
+                        if (opix[r] >= 0) {
+                            const size_t o = (size_t)opix[r] * g.Cn + col;
                             float v = acc[j][r] + bv;
                             if (res) v += res[o];
                             y[o] = v;
@@ -578,10 +625,9 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                 const float sc = scale ? scale[col] : 1.f, shf = scale ? shift[col] : 0.f;
                 const float mu = mean ? mean[col] : 0.f, is = mean ? invstd[col] : 0.f;
                 if (g.up == 2) {
-                    if (row0 < rows) {
-                        const unsigned parent = row0 >> 2;
+                    if (opix[0] >= 0) {  // the 4 rows are the children of one source pixel
                         float val = (acc[j][0] + acc[j][1]) + (acc[j][2] + acc[j][3]);
-                        const size_t o = (size_t)parent * g.Cs + col;
+                        const size_t o = (size_t)opix[0] * g.Cs + col;
                         float xv = 0.f;
                         if (relu || mean) xv = xin[o];
                         if (relu) {
@@ -597,16 +643,8 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const unsigned rr = row0 + r;
-                        if (rr < rows) {
-                            size_t o;
-                            if (g.stride == 1) {  // rows enumerate the input positions in memory order
-                                o = (size_t)rr * g.Cs + col;
-                            } else {
-                                int pn, piy, pix;
-                                dgrad_row_to_pos(g, rd, rr, py, px, pn, piy, pix);
-                                o = ((size_t)((unsigned)pn * g.Hs + piy) * g.Ws + pix) * g.Cs + col;
-                            }
+                        if (opix[r] >= 0) {
+                            const size_t o = (size_t)opix[r] * g.Cs + col;
                             float val = acc[j][r];
                             float xv = 0.f;
                             if (relu || mean) xv = xin[o];
@@ -655,7 +693,7 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
 
 // TAB (forward only): the BatchNorm affine of the input is kept in LDS -- computed by every block from the statistic slots (fold) or
 // copied from the global arrays -- and the body reads it there; TAB = false is the plain form (global arrays; any channel count).
-template <int MODE, int NT, bool VEC, bool UT, bool TAB = false>
+template <int MODE, int NT, bool VEC, bool UT, bool LIVE, bool TAB = false>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(Geom g, const float* __restrict__ S, const float* __restrict__ scale,
                                                         const float* __restrict__ shift, int relu,
                                                         const float* __restrict__ Bmat, const float* __restrict__ bias,
@@ -667,15 +705,24 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(Geom g, const float* __r
     if constexpr (TAB) {
         __shared__ __align__(16) float bn_tab[2][BN_TAB];
         bn_tab_fill(fold, scale, shift, g.Cs, bn_tab[0], bn_tab[1], (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
-        conv_gemm_body<MODE, NT, VEC, UT>(smem, g, S, bn_tab[0], bn_tab[1], relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad,
+        conv_gemm_body<MODE, NT, VEC, UT, LIVE>(smem, g, S, bn_tab[0], bn_tab[1], relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad,
                                       blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.z);
     } else {
-        conv_gemm_body<MODE, NT, VEC, UT>(smem, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad,
+        conv_gemm_body<MODE, NT, VEC, UT, LIVE>(smem, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad,
                                       blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.z);
     }
 }
 
-template <int MODE, bool VEC, bool UT>
+// Kernel-selection switch, read per call: OTVAE_GEMM_LIVE_TAPS=0 runs the vector paths in memory row order with the launch-wide
+// tap list (the form before the per-tile list; the A/B partner of tools/ab_trace.sh and the reference of the bit-equality tests).
+// Only the exact value "0" switches off (an empty or unparsable value leaves the default on): tools/conv_jobs_table.py applies the
+// same string test when it scales its executed column.
+static inline bool gemm_live_taps() {
+    const char* e = getenv("OTVAE_GEMM_LIVE_TAPS");
+    return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+template <int MODE, bool VEC, bool UT, bool LIVE>
 static void launch_gemm_v(int NT, dim3 grid, hipStream_t st, Geom g, const float* S, const float* scale, const float* shift,
                           int relu, const float* Bmat, const float* bias, const float* res, float* y, const float* xin,
                           const float* mean, const float* invstd, float* gv, double* partial, int CsPad, const BnFold& fold) {
@@ -685,12 +732,12 @@ static void launch_gemm_v(int NT, dim3 grid, hipStream_t st, Geom g, const float
     do {                                                                                                                    \
         if constexpr (MODE == 0) {                                                                                          \
             if (tab) {                                                                                                      \
-                conv_gemm_kernel<MODE, N_, VEC, UT, true><<<grid, 256, 0, st>>>(g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, \
+                conv_gemm_kernel<MODE, N_, VEC, UT, LIVE, true><<<grid, 256, 0, st>>>(g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, \
                                                                             invstd, gv, partial, CsPad, fold);              \
                 break;                                                                                                      \
             }                                                                                                               \
         }                                                                                                                   \
-        conv_gemm_kernel<MODE, N_, VEC, UT, false><<<grid, 256, 0, st>>>(g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, \
+        conv_gemm_kernel<MODE, N_, VEC, UT, LIVE, false><<<grid, 256, 0, st>>>(g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, \
                                                                      gv, partial, CsPad, fold);                             \
     } while (0)
     switch (NT) {
@@ -711,12 +758,19 @@ static void launch_gemm(int NT, dim3 grid, hipStream_t st, Geom g, const float* 
     const bool vec = (g.Cs % 4 == 0) && (g.Cn % 4 == 0) && aligned16(S) && aligned16(Bmat) &&
                      (scale == nullptr || (aligned16(scale) && aligned16(shift)));
     const int CK = MODE == 0 ? g.Cs : g.Cn;
-    if (vec && CK % KC == 0)  // a K-chunk lies inside one tap: uniform-tap pipeline
-        launch_gemm_v<MODE, true, true>(NT, grid, st, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad, fold);
-    else if (vec)
-        launch_gemm_v<MODE, true, false>(NT, grid, st, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad, fold);
-    else
-        launch_gemm_v<MODE, false, false>(NT, grid, st, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad, fold);
+#define OTVAE_LG(V_, U_, L_) \
+    launch_gemm_v<MODE, V_, U_, L_>(NT, grid, st, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad, fold)
+    const bool live = vec && gemm_live_taps();
+    if (vec && CK % KC == 0) {  // a K-chunk lies inside one tap: uniform-tap pipeline
+        if (live) OTVAE_LG(true, true, true);
+        else OTVAE_LG(true, true, false);
+    } else if (vec) {
+        if (live) OTVAE_LG(true, false, true);
+        else OTVAE_LG(true, false, false);
+    } else {
+        OTVAE_LG(false, false, false);
+    }
+#undef OTVAE_LG
 }
 
 static void fwd_grid(const Geom& g, int& NT, dim3& grid, int& CnPad) {
@@ -1489,6 +1543,68 @@ extern "C" int otvae_conv_dead_taps(const otvae_conv_geom* gg, uint32_t* mask) {
     return OTVAE_OK;
 }
 
+// (tile, tap) visits of the implicit-GEMM forward (mode 0) / data-gradient (mode 1) launch of a layer: under the launch-wide tap
+// list, and under the per-tile list of the position-major vector paths -- the same row order and the same predicate as
+// conv_gemm_body.  A layer whose channel counts are not multiples of 4 runs the scalar path: both counts are the launch-wide one.
+// The query sees the geometry only, so it assumes what launch_gemm checks besides the channel counts: 16-byte aligned activation,
+// weight and scale / shift pointers (whole tensors from torch's allocator are).  A call with a misaligned pointer falls to the
+// scalar path, where per_tile would equal launch_rule.
+extern "C" int otvae_conv_gemm_chunks(const otvae_conv_geom* gg, int mode, int64_t* launch_rule, int64_t* per_tile) {
+    int rc = check_geom(gg, "otvae_conv_gemm_chunks");
+    if (rc) return rc;
+    OTVAE_REQUIRE(mode == 0 || mode == 1, "otvae_conv_gemm_chunks: mode must be 0 (forward) or 1 (data gradient)");
+    OTVAE_REQUIRE(launch_rule && per_tile, "otvae_conv_gemm_chunks: NULL argument");
+    const Geom g = to_geom(gg);
+    {
+        TilePlan pl;
+        dim3 tg;
+        size_t sm;
+        if (conv_small_ok(g) || conv_tile_plan(g, mode, pl, tg, sm)) {
+            otvae_set_error("otvae_conv_gemm_chunks: not served by the implicit GEMM (%s kernels take this layer)",
+                            conv_small_ok(g) ? "the direct" : "the image-tile");
+            return OTVAE_EUNSUPPORTED;
+        }
+    }
+    const bool vec = (g.Cs % 4 == 0) && (g.Cn % 4 == 0);
+    const int Hu = g.Hs * g.up, Wu = g.Ws * g.up;
+    const int lim_y = mode == 0 ? Hu : g.Ho * g.stride, lim_x = mode == 0 ? Wu : g.Wo * g.stride;
+    const int last_y = mode == 0 ? (g.Ho - 1) * g.stride : Hu - 1, last_x = mode == 0 ? (g.Wo - 1) * g.stride : Wu - 1;
+    const int64_t rows = gemm_rows(g, mode), ntiles = (rows + TM - 1) / TM;
+    const int ncls = (mode == 1 && g.stride == 2) ? 4 : 1;
+    // anchors per image in position-major order (pos -> (ry, rx)); the up-2 data gradient keeps 4 children per source pixel
+    const bool kids = mode == 1 && g.up == 2;
+    const int pw = mode == 0 ? g.Wo : (g.stride == 2 ? g.Ws >> 1 : g.Ws);
+    const int64_t per_pos = (int64_t)g.N * (kids ? 4 : 1);
+    int64_t a = 0, b = 0;
+    for (int cls = 0; cls < ncls; ++cls) {
+        const int py = cls >> 1, px = cls & 1;
+        for (int kh = 0; kh < g.KH; ++kh)
+            for (int kw = 0; kw < g.KW; ++kw) {
+                int dy, dx;
+                tap_offset(mode, g.pad, kh, kw, dy, dx);
+                if (!tap_in_class(mode, g.stride, py, px, dy, dx)) continue;
+                if (!(last_y + dy >= 0 && dy < lim_y && last_x + dx >= 0 && dx < lim_x)) continue;
+                a += ntiles;
+                for (int64_t tile = 0; tile < ntiles; ++tile) {
+                    const int64_t r0 = tile * TM, r1 = (r0 + TM < rows ? r0 + TM : rows) - 1;
+                    bool hit = false;
+                    for (int64_t pos = r0 / per_pos; pos <= r1 / per_pos && !hit; ++pos) {
+                        const int y = (int)(pos / pw), x = (int)(pos % pw);
+                        for (int child = 0; child < (kids ? 4 : 1) && !hit; ++child) {  // (tiles never split a group of 4 children)
+                            const int ry = mode == 0 ? y * g.stride : (kids ? 2 * y + (child >> 1) : (g.stride == 2 ? 2 * y + py : y));
+                            const int rx = mode == 0 ? x * g.stride : (kids ? 2 * x + (child & 1) : (g.stride == 2 ? 2 * x + px : x));
+                            hit = tap_in_range(ry, rx, dy, dx, lim_y, lim_x);
+                        }
+                    }
+                    b += hit ? 1 : 0;
+                }
+            }
+    }
+    *launch_rule = a;
+    *per_tile = vec ? b : a;
+    return OTVAE_OK;
+}
+
 extern "C" int otvae_wgrad_reduce_batched(int n, const float* const* partial, const int* P, const int* K, const int* Kp,
                                           const int* Cn, float* const* gw, float* const* gb, const int* Cs,
                                           const uint32_t* dead, void* stream) {
@@ -1555,8 +1671,8 @@ struct DevJobs {
     DevJob j[CJ_MAX];
 };
 
-template <bool UT>
-__global__ __launch_bounds__(256) void conv_jobs_kernel(DevJobs t) {
+template <bool UT, bool LIVE>
+__device__ __forceinline__ void conv_jobs_body(const DevJobs& t) {
     extern __shared__ __align__(16) char jobs_smem[];
     int ji = 0;
 #pragma unroll
@@ -1575,10 +1691,10 @@ __global__ __launch_bounds__(256) void conv_jobs_kernel(DevJobs t) {
     const float* const fsc = fwd_norm ? bn_tab[0] : nullptr;
     const float* const fsh = fwd_norm ? bn_tab[1] : nullptr;
 #define CJ_FWD(N_)                                                                                                        \
-    conv_gemm_body<0, N_, true, UT>(jobs_smem, J.g, J.a0, fsc, fsh, J.relu, J.b0, J.bias, J.res, J.out, nullptr, nullptr, \
+    conv_gemm_body<0, N_, true, UT, LIVE>(jobs_smem, J.g, J.a0, fsc, fsh, J.relu, J.b0, J.bias, J.res, J.out, nullptr, nullptr, \
                                 nullptr, nullptr, J.partial, J.cpad, bx, by, bz, J.gx, J.gz)
 #define CJ_DGRAD(N_)                                                                                                      \
-    conv_gemm_body<1, N_, true, UT>(jobs_smem, J.g, J.a0, J.scale, J.shift, J.relu, J.b0, nullptr, nullptr, nullptr, J.xin,     \
+    conv_gemm_body<1, N_, true, UT, LIVE>(jobs_smem, J.g, J.a0, J.scale, J.shift, J.relu, J.b0, nullptr, nullptr, nullptr, J.xin,     \
                                 J.mean, J.invstd, J.out, J.partial, J.cpad, bx, by, bz, J.gx, J.gz)
 #define CJ_WGRAD(N_) \
     conv_wgrad_body<N_, true>(jobs_smem, J.g, J.a0, J.scale, J.shift, J.relu, J.b0, J.out, J.Kp, J.has_bias, J.skip_dead, \
@@ -1600,6 +1716,16 @@ __global__ __launch_bounds__(256) void conv_jobs_kernel(DevJobs t) {
 #undef CJ_FWD
 #undef CJ_DGRAD
 #undef CJ_WGRAD
+}
+
+template <bool UT>
+__global__ __launch_bounds__(256) void conv_jobs_kernel(DevJobs t) {
+    conv_jobs_body<UT, true>(t);
+}
+// OTVAE_GEMM_LIVE_TAPS=0: memory row order, launch-wide tap lists
+template <bool UT>
+__global__ __launch_bounds__(256) void conv_jobs_rowmajor_kernel(DevJobs t) {
+    conv_jobs_body<UT, false>(t);
 }
 
 static size_t job_smem_bytes(int kind, int NT) {
@@ -1667,10 +1793,14 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
             pack_ut = -1;
             return rc;
         }
-        if (pack_ut == 1)
-            conv_jobs_kernel<true><<<nblocks, 256, smem, st>>>(pack);
-        else
-            conv_jobs_kernel<false><<<nblocks, 256, smem, st>>>(pack);
+        const bool live = gemm_live_taps();
+        if (pack_ut == 1) {
+            if (live) conv_jobs_kernel<true><<<nblocks, 256, smem, st>>>(pack);
+            else conv_jobs_rowmajor_kernel<true><<<nblocks, 256, smem, st>>>(pack);
+        } else {
+            if (live) conv_jobs_kernel<false><<<nblocks, 256, smem, st>>>(pack);
+            else conv_jobs_rowmajor_kernel<false><<<nblocks, 256, smem, st>>>(pack);
+        }
         OTVAE_CHECK_LAUNCH("otvae_conv_multi");
         for (int i = 0; i < pack.n; ++i) g_multi_packed_mask |= 1u << packed_idx[i];
         g_multi_packed_ut = pack_ut == 1 ? 1 : 0;

@@ -10,6 +10,7 @@ for side in a b; do
   if [ $side = a ]; then export "$1"; else export "$2"; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_$side" -- python3 "$R/bench.py" --steps 30 --warmup 5 --no-cpu-baseline > "$O/bench_$side.json" 2> "$O/trace_$side.err"
   OTVAE_PROFILES_OUT="$O/profiles" python3 "$R/tools/summarize_profiles.py" --replay "$O/trace_$side" ab_$side
+  OTVAE_PROFILES_OUT="$O/profiles" python3 "$R/tools/summarize_profiles.py" --launches "$O/trace_$side" ab_$side
   rm -rf "$O/trace_$side"
 done
 echo "[ab] done"

@@ -17,6 +17,21 @@ from ot_vae_lightning_amd.utils.synthetic import mnist_like  # noqa: E402
 KIND = {0: "fwd", 1: "dgrad", 2: "wgrad"}
 
 
+def executed_flops(lib, j):
+    """MACs x 2 the kernel issues for one job: bench.py's count under the launch-wide tap rule, scaled -- where the implicit GEMM
+    serves a forward / data-gradient job and OTVAE_GEMM_LIVE_TAPS is not 0 -- by the (tile, tap) visits of the per-tile tap list over
+    those of the launch-wide one (otvae_conv_gemm_chunks: the kernel's own row order and predicate)."""
+    fx = bench._job_flops(j)["executed"]
+    if j["kind"] == L.JOB_BWD_WEIGHT or os.environ.get("OTVAE_GEMM_LIVE_TAPS") == "0":
+        return fx
+    launch, tile = C.c_int64(0), C.c_int64(0)
+    rc = lib.otvae_conv_gemm_chunks(C.byref(L.ConvGeom(*j["geom"])), j["kind"], C.byref(launch), C.byref(tile))
+    if rc == -2:    # the image-tile or direct kernels take the layer
+        return fx
+    L.check(rc, "otvae_conv_gemm_chunks")
+    return fx * tile.value / launch.value
+
+
 def main(all_calls=False):
     lib = L.load()
     model = bench.build_model(A, seed=2).cuda().train()
@@ -39,13 +54,13 @@ def main(all_calls=False):
             b_, f_ = bench._job_algorithmic(j)      # bytes, LIVE flops (operands that exist; round 3 printed the padded count)
             by += b_
             fl += f_
-            flx += bench._job_flops(j)["executed"]
+            flx += executed_flops(lib, j)
             flp += bench._job_flops(j)["padded"]
             desc.append(f"{KIND[j['kind']]}{'*' if c['packed_mask'] >> i & 1 else ''} {g['Cs']}->{g['Cn']} k{g['KH']} s{g['stride']} up{g['up']} "
                         f"{g['Hs']}x{g['Ws']}->{g['Ho']}x{g['Wo']}")
         rows.append((ci, c["uniform_tap"], c["packed_mask"], by, (fl, flx, flp), " | ".join(desc)))
     # time every call alone (re-issued on synthetic tensors through bench's builder, one call per graph)
-    print("FLOP columns: live (operands that exist) / executed by the kernel (dead taps dropped) / padded (2*y*KH*KW*Cs, rounds 1-3); TF/s and the\n"
+    print("FLOP columns: live (operands that exist) / executed by the kernel (taps no row of a tile can use dropped) / padded (2*y*KH*KW*Cs, rounds 1-3); TF/s and the\n"
           "fraction of the 157.3 TFLOP/s fp32 matrix peak are for the LIVE count; no launch may exceed 1.0 of a hardware peak")
     worst = 0.0
     for ci, ut, mask, by, (fl, flx, flp), desc in rows:

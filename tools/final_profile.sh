@@ -2,7 +2,7 @@
 # Collects everything profiles/ is built from, on the GPU box (run through gpurun from the repo root):
 #   gpurun_out/final/trace        rocprofv3 --kernel-trace --stats of the default bench command
 #   gpurun_out/final/pmc_*        separate PMC passes (MI355X_MICROARCH.md: one counter group per pass): FETCH_SIZE, WRITE_SIZE,
-#                                 MFMA busy, SQ instruction / wait counters
+#                                 MFMA busy (these three without any tracing), SQ instruction / wait counters
 #   gpurun_out/final/trace_sk     kernel trace of the Sinkhorn workload (configs[2])
 #   gpurun_out/final/bench*.json  un-profiled bench lines (MNIST/Gaussian default, Sinkhorn workload)
 #   gpurun_out/final/*.txt        OT path timings, eigensolver timings, OT gradient micro-benchmark, per-call conv table
@@ -14,11 +14,11 @@ rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- python3 "$R/bench.py" --full > "$O/trace_bench.json" 2> "$O/trace.err"
 echo "[final] trace done"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$O/pmc_fetch" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_fetch.json" 2> "$O/pmc_fetch.err"
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pmc_fetch" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_fetch.json" 2> "$O/pmc_fetch.err"
 echo "[final] pmc fetch done"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$O/pmc_write" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_write.json" 2> "$O/pmc_write.err"
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/pmc_write" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_write.json" 2> "$O/pmc_write.err"
 echo "[final] pmc write done"
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$O/pmc_mfma" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_mfma.json" 2> "$O/pmc_mfma.err"
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$O/pmc_mfma" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_mfma.json" 2> "$O/pmc_mfma.err"
 echo "[final] pmc mfma done"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES --kernel-trace --output-format csv -d "$O/pmc_sq" -- python3 "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$O/pmc_sq.json" 2> "$O/pmc_sq.err"
 echo "[final] pmc sq done"

@@ -2,6 +2,7 @@
 
     python tools/summarize_profiles.py <kernel-stats dir> <tag>         # e.g. gpurun_out/prof8 r01_final
     python tools/summarize_profiles.py --replay <kernel-trace dir> <tag> # replayed (timed) steps only
+    python tools/summarize_profiles.py --launches <kernel-trace dir> <tag> # every implicit-GEMM conv launch of a step, in order
     python tools/summarize_profiles.py --pmc gpurun_out <tag>           # pmc_fetch / pmc_write / pmc_mfma passes
     python tools/summarize_profiles.py --roofline <tag>                 # joins the replay and PMC summaries
     python tools/summarize_profiles.py --pmc-sq <pmc_sq dir> <tag>      # SQ issue / wait counters per kernel
@@ -68,6 +69,33 @@ def replay_stats(src, tag, steps=20):
     print("wrote", out, "launches/step", len(seg) // steps, "busy ms/step %.3f wall %.3f" % (tot / 1e6 / steps, wall / 1e6 / steps))
 
 
+def launch_list(src, tag, names=("conv_gemm_kernel", "conv_jobs_")):
+    """Every launch of the named kernels inside one step, in start order, with its duration averaged over the same 20 replays as
+    replay_stats: the per-launch view of an A/B (a per-kernel average hides which layer's launch moved)."""
+    f = max(glob.glob(os.path.join(src, "*", "*_kernel_trace.csv")), key=os.path.getmtime)
+    rows = list(csv.DictReader(open(f)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    ends = [i for i, r in enumerate(rows) if r["Kernel_Name"].startswith("adam_kernel")]
+    t_end = [int(rows[i]["End_Timestamp"]) for i in ends]
+    steps = 20
+    best = min(range(len(ends) - steps), key=lambda a: t_end[a + steps] - t_end[a])
+    per_step = []
+    for s in range(steps):
+        seg = rows[ends[best + s] + 1: ends[best + s + 1] + 1]
+        per_step.append([(r["Kernel_Name"].split("(")[0], r.get("Grid_Size", "?"), int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+                         for r in seg if any(n in r["Kernel_Name"] for n in names)])
+    n = min(len(p) for p in per_step)
+    if any(len(p) != n for p in per_step):
+        print("warning: the replays differ in their launch counts; listing the first", n)
+    out = os.path.join(OUT, f"{tag}_launches.txt")
+    with open(out, "w") as w:
+        w.write("# launch index in the step, mean us over %d replays, min, max, grid size (threads), kernel\n" % steps)
+        for i, (k, grid, _) in enumerate(per_step[0][:n]):
+            d = [p[i][2] / 1e3 for p in per_step]
+            w.write("%3d %8.2f %8.2f %8.2f %9s  %s\n" % (i, sum(d) / len(d), min(d), max(d), grid, k[:80]))
+    print("wrote", out, n, "launches per step")
+
+
 def timeline(src, tag):
     """ONE graph replay (the 10th of the fastest 20-step window) as a timeline: start / end of every launch in us from the step's first
     kernel, the queue it ran on, the idle gap on that queue in front of it: where the chain waits, what ends the step."""
@@ -116,7 +144,7 @@ def pmc(src, tag):
                 k = x["Kernel_Name"].split("(")[0]
                 a[k][0] += 1
                 a[k][1] += float(x["Counter_Value"])
-                a[k][2] += (int(x["End_Timestamp"]) - int(x["Start_Timestamp"]))
+                a[k][2] += int(x.get("End_Timestamp") or 0) - int(x.get("Start_Timestamp") or 0)  # (a pass without tracing may carry none)
         return a
     F, W = load("pmc_fetch", "FETCH_SIZE"), load("pmc_write", "WRITE_SIZE")
     MF, GA = load("pmc_mfma", "SQ_VALU_MFMA_BUSY_CYCLES"), load("pmc_mfma", "GRBM_GUI_ACTIVE")
@@ -210,6 +238,8 @@ if __name__ == "__main__":
         pmc(sys.argv[2], sys.argv[3])
     elif sys.argv[1] == "--replay":
         replay_stats(sys.argv[2], sys.argv[3])
+    elif sys.argv[1] == "--launches":
+        launch_list(sys.argv[2], sys.argv[3])
     elif sys.argv[1] == "--timeline":
         timeline(sys.argv[2], sys.argv[3])
     else:
