@@ -734,6 +734,33 @@ int otvae_ar_layer_step(const float* x, int B, int D, int H, int F, int pos, int
 int otvae_ar_embed_step(const int64_t* ids, int64_t ids_stride, int pos, int B, int D, int V, int P, const float* vocab,
                         const float* positions, const float* ln_g, const float* ln_b, float eps, float* out, void* stream);
 
+/* ---- image transforms around the model ------------------------------------------------------------------------------------------------ */
+/* torchvision.transforms.functional.gaussian_blur, the degradation of the reference's latent-transport experiments
+ * (tests/test_latent_transport.py:35, tests/test_conditional_vit_vae.py:91-95: GaussianBlur(5, sigma=(1.5, 1.5))): every channel of
+ * x [N][C][H][W] is reflect-padded by (kx / 2, ky / 2) without edge repeat (F.pad(mode="reflect")) and correlated with the window
+ * wy[ky] x wx[kx].  wx / wy are HOST arrays (they travel in the kernel's argument block): the caller evaluates torchvision's
+ * _get_gaussian_kernel1d in fp32.  channels_last = 0: x and y are NCHW-contiguous; 1: both are NHWC memory (the package's layout); the
+ * output has the layout of the input, no converted or padded copy is made.  One launch, no atomics; a plane's result does not depend
+ * on N or on its place in the batch; kx = ky = 1 with weight 1 returns the input's bits.
+ * OTVAE_EINVAL: null pointers, even or non-positive kernel sizes.  OTVAE_EUNSUPPORTED outside the envelope: kx, ky <= 31,
+ * kx / 2 < W and ky / 2 < H (what reflect padding itself requires), N * C * H * W < 2^31. */
+int otvae_gaussian_blur_fwd(const float* x, int N, int C, int H, int W, int channels_last, int kx, int ky, const float* wx,
+                            const float* wy, float* y, void* stream);
+/* Its adjoint (what autograd derives from F.pad(mode="reflect") + F.conv2d): per axis, with p = k / 2 and gy extended by zeros,
+ * G(m) = sum_t w[t] gy[m + p - t] and gx[i] = G(i) + [1 <= i <= p] G(-i) + [H-1-p <= i <= H-2] G(2 (H-1) - i).  A gather in a fixed
+ * order, no atomics.  Arguments and envelope as the forward entry. */
+int otvae_gaussian_blur_bwd(const float* gy, int N, int C, int H, int W, int channels_last, int kx, int ky, const float* wx,
+                            const float* wy, float* gx, void* stream);
+/* Collage.list_to_collage (utils/collage.py:112-121: torch.cat(images, -1).clamp(0, 1), torchvision's make_grid(nrow=1, padding=2,
+ * pad_value=0)) without the concatenated temporary: the first n samples of L <= 16 maps [B][C][H][W_l] side by side, clamped to [0, 1],
+ * a single channel repeated three times (C' = 3 if C == 1 else C); sample k at row k (H + 2) + 2, column 2 of a zero-bordered
+ * [n (H + 2) + 2][sum W_l + 4] grid, or for n == 1 the bare [H][sum W_l] image, as make_grid returns it.
+ * maps: HOST array of L device pointers; strides: HOST int64 [L][4], the (sample, channel, row, pixel) strides of each map in elements
+ * (any layout is read in place); widths: HOST int [L].  as_uint8 = 0: out is fp32 [C'][OH][OW], what the loggers take; 1: out is
+ * uint8 [OH][OW][C'] = trunc(clamp(v * 255 + 0.5, 0, 255)), torchvision.utils.save_image's quantisation. */
+int otvae_collage(const float* const* maps, const int64_t* strides, const int* widths, int L, int n, int C, int H, int as_uint8,
+                  void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ pp = C.POINTER(C.c_void_p)  # host array of device pointers
 pi32 = C.POINTER(C.c_int)
 pu32 = C.POINTER(C.c_uint32)
 pi64 = C.POINTER(C.c_int64)
+pf32 = C.POINTER(C.c_float)  # host array of floats
 
 
 class ConvGeom(C.Structure):
@@ -192,6 +193,9 @@ SIGNATURES = {
     "otvae_codebook_gather": (i32, [vp, vp, i64, i32, i32, vp, vp]),
     "otvae_ar_layer_step": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp]),
     "otvae_ar_embed_step": (i32, [vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, vp]),
+    "otvae_gaussian_blur_fwd": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, pf32, pf32, vp, vp]),
+    "otvae_gaussian_blur_bwd": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, pf32, pf32, vp, vp]),
+    "otvae_collage": (i32, [pp, pi64, pi32, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 

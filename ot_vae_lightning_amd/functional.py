@@ -2157,3 +2157,62 @@ def ar_layer_step(x: Tensor, pos: int, heads: int, in_proj_weight: Tensor, in_pr
                                           ptr(linear1_bias), ptr(linear2_weight), ptr(linear2_bias), ptr(norm2_weight), ptr(norm2_bias),
                                           float(eps2), ptr(kcache), ptr(vcache), ptr(y), stream()), "otvae_ar_layer_step")
     return y
+
+
+# ------------------------------------------------------------------------------------------------ image transforms
+def _blur_pair(value, what: str) -> tuple:
+    if isinstance(value, (int, float)):
+        return value, value
+    if isinstance(value, (list, tuple)) and len(value) == 1:
+        return value[0], value[0]
+    if not isinstance(value, (list, tuple)) or len(value) != 2:
+        raise ValueError(f"If {what} is a sequence its length should be 2. Got {value}")
+    return tuple(value)
+
+
+def gaussian_blur(img: Tensor, kernel_size, sigma) -> Tensor:
+    """torchvision's ``transforms.functional.gaussian_blur`` on the device: reflect padding by ``k // 2`` and the separable Gaussian
+    window in one launch, without a padded copy (``torch.ops.otvae.gaussian_blur``).  ``kernel_size`` = k or (kx, ky), ``sigma`` = s or
+    (sigma_x, sigma_y), torchvision's order.  ``img``: float32 [C, H, W] or [N, C, H, W], NCHW-contiguous or channels-last; the result
+    keeps the input's layout.  Differentiable in ``img``."""
+    kx, ky = _blur_pair(kernel_size, "kernel_size")
+    sx, sy = _blur_pair(sigma, "sigma")
+    for k in (kx, ky):
+        if not isinstance(k, int) or isinstance(k, bool) or k % 2 == 0 or k <= 0:
+            raise ValueError(f"kernel_size should have odd and positive integers. Got {kernel_size}")
+    for s in (sx, sy):
+        if not s > 0.:
+            raise ValueError(f"sigma should have positive values. Got {sigma}")
+    return torch.ops.otvae.gaussian_blur(img, kx, ky, float(sx), float(sy))
+
+
+@torch.no_grad()
+def collage(images: Sequence[Tensor], num_samples: int, as_uint8: bool = False) -> Tensor:
+    """The reference's ``Collage.list_to_collage`` (utils/collage.py:112-121) in one launch: the first ``min(B, num_samples)`` samples of
+    the maps ``[B, C, H, W_l]`` side by side, clamped to [0, 1], a single channel repeated three times, laid out as torchvision's
+    ``make_grid(nrow=1)`` (2 pixels of zero padding; a single sample comes back bare).  Every map is read in place, whatever its layout:
+    there is no concatenated temporary.  Returns float32 ``[C', OH, OW]``, or with ``as_uint8`` the uint8 ``[OH, OW, C']`` image that
+    torchvision's ``save_image`` would write."""
+    images = list(images)
+    if not images:
+        raise ValueError("collage needs at least one map")
+    b, c, h = images[0].shape[:3]
+    for t in images:
+        _lib.require_cuda(t, "collage map")
+        if t.dtype != torch.float32:
+            raise NotImplementedError(f"collage takes float32 maps, got {t.dtype}")
+        if t.dim() != 4 or tuple(t.shape[:3]) != (b, c, h):
+            raise ValueError(f"collage takes maps [B, C, H, W_l] with the same B, C, H: {[tuple(t.shape) for t in images]}")
+    n = min(b, int(num_samples))
+    if n <= 0:
+        raise ValueError(f"collage of {n} samples (batch {b}, num_samples {num_samples})")
+    count = len(images)
+    pad = 0 if n == 1 else 2
+    oh, ow, cout = n * (h + pad) + pad, sum(t.shape[3] for t in images) + 2 * pad, 3 if c == 1 else c
+    out = torch.empty((oh, ow, cout), device=images[0].device, dtype=torch.uint8) if as_uint8 else \
+        torch.empty((cout, oh, ow), device=images[0].device, dtype=torch.float32)
+    strides = (C.c_int64 * (4 * count))(*[s for t in images for s in t.stride()])
+    widths = (C.c_int * count)(*[t.shape[3] for t in images])
+    check(_lib.load().otvae_collage(ptr_array(images), strides, widths, count, n, c, h, int(bool(as_uint8)), ptr(out), stream()),
+          "otvae_collage")
+    return out

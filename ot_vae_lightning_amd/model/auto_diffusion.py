@@ -11,14 +11,14 @@ Differences from the reference, all deliberate:
   * the beta weighting lives in ``per_sample_prior_loss`` (the fused loss reduction takes the [B] vector); ``prior_loss`` is its mean,
     as the reference's override computes;
   * ``sample`` does not swallow a ``RuntimeError`` into an empty list, and ``FilterKwargs`` is not patched: ``VAE`` forwards every
-    keyword by the callee's signature already;
-  * ``reconstruction`` / ``generation`` / ``generation_improved`` return the reference's lists without the ``Collage`` decorator."""
+    keyword by the callee's signature already."""
 from typing import List, Optional, Union
 
 import numpy as np
 import torch
 from torch import Tensor
 
+from ..utils import Collage
 from .vae import VAE
 
 __all__ = ["AutoDiffusion"]
@@ -91,15 +91,18 @@ class AutoDiffusion(VAE):
     def _generation_steps(self) -> List[int]:
         return [int(i) for i in np.linspace(0, self.n_steps, 10)]   # (n_steps itself is never reached: 9 images at n_steps = 10)
 
+    @Collage.log_method
     def reconstruction(self, batch: VAE.Batch) -> List[Tensor]:
         samples, target, kwargs = batch["samples"], batch["target"], batch["kwargs"]
         ones = torch.ones_like(kwargs["time"])
         return [self(samples, **{**kwargs, "time": ones * t}) for t in np.linspace(0, 1, 10)] + [target]
 
+    @Collage.log_method
     def generation(self, batch: VAE.Batch) -> List[Tensor]:
         samples, kwargs = batch["samples"], batch["kwargs"]
         return self.sample(samples.size(0), steps=self._generation_steps(), improved_algorithm=False, **kwargs)
 
+    @Collage.log_method
     def generation_improved(self, batch: VAE.Batch) -> List[Tensor]:
         samples, kwargs = batch["samples"], batch["kwargs"]
         return self.sample(samples.size(0), steps=self._generation_steps(), improved_algorithm=True, **kwargs)

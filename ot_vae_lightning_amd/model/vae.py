@@ -3,7 +3,7 @@
 ``latent_size``, ``configure_optimizers``.  The reduction mse + mean(prior)/(C*H*W) is one fused kernel."""
 import functools
 import itertools
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -13,7 +13,8 @@ from torch import Tensor
 from .. import functional as HF
 from .. import utils
 from ..prior import Prior
-from ..utils import FilterKwargs
+from ..transforms import transform_batch_tv
+from ..utils import Collage, FilterKwargs
 from .base import VisionModule
 
 __all__ = ["VAE"]
@@ -51,7 +52,12 @@ class VAE(VisionModule):
         self._filter = lambda callee, keys=("labels", "eps"): FilterKwargs(callee, arg_keys=list(keys))
 
     # -- reference API -------------------------------------------------------------------------------------------
+    @transform_batch_tv()
     def batch_preprocess(self, batch) -> Batch:
+        """``(samples, labels)`` -> the step's batch dict (reference model/vae.py:125-133).  The samples pass through the transform a
+        ``transforms.ProgressiveTransform`` installed on this instance (none: they come back as the same object).  This runs outside
+        the captured step -- ``enable_graphed_step()`` copies the result into the graph's static input -- so a transform that changes
+        per epoch is safe with a graphed step."""
         samples, labels = batch
         return {"samples": samples, "target": samples, "kwargs": {"labels": labels} if self.conditional else {}}
 
@@ -165,3 +171,20 @@ class VAE(VisionModule):
         else:
             latents = torch.randn((batch_size, *self.latent_size), device=self.device)
         return self.decode(latents, **kwargs, no_postprocess_override=True)
+
+    @Collage.log_method
+    def reconstruction(self, batch: Batch) -> List[Tensor]:
+        """[target, mean reconstruction, the `expansion` realisations, their std] (reference model/vae.py:240-248)"""
+        samples, target, kwargs = batch["samples"], batch["target"], batch["kwargs"]
+        batch_size = samples.size(0)
+        reconstructions = self(samples, expand=True, **kwargs)
+        reconstructions_mean = self._reduce_mean(reconstructions)
+        reconstructions_std = self._reduce_std(reconstructions)
+        realizations = [reconstructions[batch_size * i:batch_size * (i + 1)] for i in range(self.expansion)]
+        return [target, reconstructions_mean, *realizations, reconstructions_std]
+
+    @Collage.log_method
+    def generation(self, batch: Batch) -> List[Tensor]:
+        """four times the batch of prior samples, decoded, as four columns (reference model/vae.py:250-253)"""
+        samples, kwargs = batch["samples"], batch["kwargs"]
+        return list(self.sample(samples.size(0) * 4, **kwargs).chunk(4, dim=0))

@@ -12,17 +12,20 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
     otvae::gaussian_w2_prior        _stats -> mean_cov -> w2_gaussian            gaussian_model.py:144-157, matrix_utils.py:145-158,
                                                                                  w2_utils.py:40-80
     otvae::soft_cross_entropy       DAD.prior_loss's shifted soft-label CE       model/discrete_auto_diffuser.py:63-72
+    otvae::gaussian_blur            torchvision's gaussian_blur (GaussianBlur)   tests/test_latent_transport.py:35
 
     otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
     otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
 
 The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the two OT priors,
-``soft_cross_entropy``).
+``soft_cross_entropy``, ``gaussian_blur``).
 ``ConvBlock`` runs its two branches and the training engine's in-place gradient slots through the packed variant of the
 same kernels (``functional.conv_layers``); ``otvae::conv_bn_act`` is the single-layer functional form.
 """
 from __future__ import annotations
 
+import ctypes as C
+import functools
 from typing import Optional, Tuple
 
 import torch
@@ -34,7 +37,7 @@ from ._lib import check, ptr, stream
 __all__ = ["OPS"]
 
 OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior",
-       "soft_cross_entropy")
+       "soft_cross_entropy", "gaussian_blur")
 _lib_def = torch.library.Library("otvae", "DEF")
 
 
@@ -519,6 +522,76 @@ def _sce_backward(ctx, gloss, _glse, _gpsum):
 
 
 torch.library.register_autograd("otvae::soft_cross_entropy", _sce_backward, setup_context=_sce_setup)
+
+
+# ------------------------------------------------------------------------------------------------ GaussianBlur
+@functools.lru_cache(maxsize=64)
+def _gaussian_kernel1d(kernel_size: int, sigma: float):
+    """torchvision's ``_get_gaussian_kernel1d`` in fp32 on the host, as a ctypes array for the kernel's argument block"""
+    half = (kernel_size - 1) * 0.5
+    x = torch.linspace(-half, half, steps=kernel_size)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    return (C.c_float * kernel_size)(*(pdf / pdf.sum()).tolist())
+
+
+def _blur_call(entry: str, img: Tensor, kx: int, ky: int, sx: float, sy: float) -> Tensor:
+    """``img``: fp32 [C, H, W] or [N, C, H, W], NCHW-contiguous or channels-last (any other striding is made contiguous first); the
+    result has the layout of the input."""
+    lib = _lib.load()
+    _lib.require_cuda(img, "gaussian_blur input")
+    if img.dtype != torch.float32:
+        raise NotImplementedError(f"gaussian_blur computes in float32, got {img.dtype}")
+    if img.dim() not in (3, 4):
+        raise ValueError(f"gaussian_blur takes [C, H, W] or [N, C, H, W] images, got {tuple(img.shape)}")
+    x4 = img if img.dim() == 4 else img.unsqueeze(0)
+    n, c, h, w = x4.shape
+    if kx // 2 >= w or ky // 2 >= h:   # F.pad(mode="reflect")'s own refusal, in its words
+        raise RuntimeError(f"Padding size should be less than the corresponding input dimension, but got: padding ({kx // 2}, {kx // 2}) "
+                           f"at dimension 3 and ({ky // 2}, {ky // 2}) at dimension 2 of input {list(x4.shape)}")
+    if x4.numel() == 0:
+        return torch.empty_like(img)
+    from .functional import is_nhwc
+    if x4.is_contiguous():
+        channels_last = 0
+    elif is_nhwc(x4):
+        channels_last = 1
+    else:
+        x4, channels_last = x4.contiguous(), 0
+    out = torch.empty_strided(x4.shape, x4.stride(), device=x4.device, dtype=x4.dtype)
+    check(getattr(lib, entry)(ptr(x4), n, c, h, w, channels_last, kx, ky, _gaussian_kernel1d(kx, sx), _gaussian_kernel1d(ky, sy),
+                              ptr(out), stream()), entry)
+    return out if img.dim() == 4 else out.squeeze(0)
+
+
+def _blur_fwd(img: Tensor, kx: int, ky: int, sx: float, sy: float) -> Tensor:
+    return _blur_call("otvae_gaussian_blur_fwd", img, kx, ky, sx, sy)
+
+
+def _blur_bwd(gout: Tensor, kx: int, ky: int, sx: float, sy: float) -> Tensor:
+    return _blur_call("otvae_gaussian_blur_bwd", gout, kx, ky, sx, sy)
+
+
+def _blur_fake(img, kx, ky, sx, sy):
+    from .functional import is_nhwc
+    x4 = img if img.dim() == 4 else img.unsqueeze(0)
+    dense = x4.is_contiguous() or is_nhwc(x4)
+    return torch.empty_strided(img.shape, img.stride(), device=img.device, dtype=img.dtype) if dense else \
+        torch.empty(img.shape, device=img.device, dtype=img.dtype)
+
+
+_define("gaussian_blur", "(Tensor img, int kx, int ky, float sigma_x, float sigma_y) -> Tensor", _blur_fwd, _blur_fake)
+_define("gaussian_blur_backward", "(Tensor gout, int kx, int ky, float sigma_x, float sigma_y) -> Tensor", _blur_bwd, _blur_fake)
+
+
+def _blur_setup(ctx, inputs, output):
+    ctx.cfg = inputs[1:]
+
+
+def _blur_backward(ctx, gout):
+    return torch.ops.otvae.gaussian_blur_backward(gout, *ctx.cfg), None, None, None, None
+
+
+torch.library.register_autograd("otvae::gaussian_blur", _blur_backward, setup_context=_blur_setup)
 
 
 # ------------------------------------------------------------------------------------------------ validation metrics

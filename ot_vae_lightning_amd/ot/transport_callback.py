@@ -92,6 +92,31 @@ class LatentTransport:
             raise NotImplementedError(f"cannot sample from `{from_dist}`: 'source' or 'target'")
         return self._unflatten_and_unpermute(dist.sample((n,)))
 
+    @torch.no_grad()
+    def _collage(self, trainer, pl_module) -> Optional[Tensor]:
+        """The reference's picture of the experiment (transport_callback.py:299-315), six columns per validation sample: decoded source
+        prior draws | transformed | transformed, decoded | transported, decoded | real | decoded target prior draws."""
+        batch = pl_module.batch_preprocess(next(iter(trainer.val_dataloaders[0])))
+        samples, kwargs = self._get_samples(pl_module, batch)
+        # one sample at a time, as the reference does, in case the transformation does not take batches
+        transformed = torch.stack([self.transformations(sample) for sample in samples])
+        latents = self._encode(pl_module, transformed, **kwargs)
+        transformed_decoded = self._decode(pl_module, latents, **kwargs)
+        samples_transported = self._decode(pl_module, self.transport(latents), **kwargs)
+        samples_source = self._decode(pl_module, self.sample(latents.size(0), "source").type_as(latents), **kwargs)
+        samples_target = self._decode(pl_module, self.sample(latents.size(0), "target").type_as(latents), **kwargs)
+        img_list = [samples_source, transformed, transformed_decoded, samples_transported, samples, samples_target]
+        return utils.Collage.list_to_collage(img_list, min(samples.shape[0], self.num_samples_to_log))
+
+    def _log_images(self, trainer, pl_module) -> None:
+        """transport_callback.py:378-385; nothing without a trainer that holds validation data"""
+        if self.num_samples_to_log <= 0 or trainer is None or not getattr(trainer, "val_dataloaders", None):
+            return
+        collage = self._collage(trainer, pl_module)
+        logger = getattr(trainer, "logger", None)
+        if hasattr(logger, "log_image"):
+            logger.log_image(self.logging_prefix, [collage], getattr(trainer, "global_step", 0))
+
     def _get_samples(self, pl_module, outputs) -> Tuple[Tensor, Dict[str, Any]]:
         if not isinstance(outputs, dict):
             raise ValueError(f"the step must return a dict, got {type(outputs)}")
@@ -190,6 +215,7 @@ class LatentTransport:
         if getattr(trainer, "sanity_checking", False) and (self.source_latents_from_train or self.target_latents_from_train):
             return
         self._log(pl_module, self.logging_prefix + "avg_transport_cost", self.transport_operator.compute().mean())
+        self._log_images(trainer, pl_module)
 
     def on_test_epoch_start(self, trainer, pl_module) -> None:
         if self.test_metrics is not None:

@@ -16,7 +16,7 @@ from torch import Tensor
 
 __all__ = ["DDPMixin", "FilterKwargs", "hasarg", "replicate_batch", "mean_replicated_batch", "std_replicated_batch",
            "ema", "laplace_smoothing", "permute_and_flatten", "unflatten_and_unpermute", "unsqueeze_like", "ddp_reduce_sum",
-           "ddp_gather_all", "apply_to_collection", "ema_inplace", "VectorLayout", "PartialCheckpoint", "human_format"]
+           "ddp_gather_all", "apply_to_collection", "ema_inplace", "VectorLayout", "PartialCheckpoint", "human_format", "Collage"]
 
 
 def _dist_on() -> bool:
@@ -220,3 +220,4 @@ def unsqueeze_like(tensor: Tensor, like: Tensor) -> Tensor:
 
 
 from .partial_checkpoint import PartialCheckpoint, human_format  # noqa: E402
+from .collage import Collage  # noqa: E402
