@@ -540,6 +540,22 @@ int otvae_sqdist_max(int dtype, const void* x, const void* y, int nb, int N, int
 int otvae_ot_cost_grad(int dtype, const void* z, const void* y, const void* pi, const void* g, int ng, double scale,
                        const void* gadd, int N, int M, int D, void* gz, void* stream);
 
+/* ---- sliced Wasserstein-2 between latents and prior draws (SlicedWassersteinPrior; SURVEY F3: no reference class) ------- */
+/* z[N][D], y[N][D], dirs[L][D] (raw direction draws), all fp32.  theta_l = dirs_l / |dirs_l| (written to theta[L][D]); p = z theta^T,
+ * q = y theta^T; every column of p (with its row indices) and of q is sorted in LDS by a bitonic network padded with +inf to the next
+ * power of two, ties by the smaller original row.  resid[l][i] = p_l,i - q_l,(rank_l(i)) in ORIGINAL row order;
+ * loss[loss_rep] = scale / (L N) sum_l sum_i resid[l][i]^2, the same value loss_rep times (prior/base.py:74-78).  One workgroup per
+ * projection leaves an fp64 partial in ws (otvae_sliced_w2_ws bytes, 8-byte aligned); a one-block second launch sums them in index order:
+ * the loss is bit-reproducible and no float atomic is used.  A projection that is not finite makes the loss NaN.
+ * Envelope: 1 <= N <= 4096, D >= 1, L >= 1; beyond it OTVAE_EUNSUPPORTED (otvae_sliced_w2_ws: -1). */
+int64_t otvae_sliced_w2_ws(int N, int L);
+int otvae_sliced_w2_fwd(const float* z, const float* y, const float* dirs, int N, int D, int L, double scale, int loss_rep, void* ws,
+                        float* theta, float* resid, float* loss, void* stream);
+/* gz[i][d] = (gadd ? gadd[i][d] : 0) + (sum_b gout[b]) scale 2 / (L N) sum_l resid[l][i] theta[l][d]; gout[N] are the upstream gradients
+ * of the loss replicas, gadd[N][D] (may be NULL) the gradient reaching z through its other consumer.  One launch, fixed summation order. */
+int otvae_sliced_w2_bwd(const float* gout, const float* gadd, const float* resid, const float* theta, int N, int D, int L,
+                        double scale, float* gz, void* stream);
+
 /* ---- Gaussian W2 with empirical covariance as a loss term (GaussianW2Prior; BASELINE north_star) ------------ */
 /* Forward tail of L = w2_gaussian(mean_cov(_stats(z)), N(mut, covt)) (ot/w2_utils.py:40-80, ot/matrix_utils.py:145-158,
  * gaussian_model.py:144-157): lam[D], vt[D][D] = eigenvalues / eigenvector rows of M = covt^1/2 cov covt^1/2 (otvae_eigh_fn,

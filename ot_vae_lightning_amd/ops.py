@@ -11,13 +11,15 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
     otvae::sinkhorn_prior           sq. euclidean cost -> sinkhorn_log -> <C,pi> ot/w2_utils.py:265-269,276-319
     otvae::gaussian_w2_prior        _stats -> mean_cov -> w2_gaussian            gaussian_model.py:144-157, matrix_utils.py:145-158,
                                                                                  w2_utils.py:40-80
+    otvae::sliced_w2                sliced Wasserstein-2 (sort and match per     no reference class (SURVEY.md F3)
+                                    projection)
     otvae::soft_cross_entropy       DAD.prior_loss's shifted soft-label CE       model/discrete_auto_diffuser.py:63-72
     otvae::gaussian_blur            torchvision's gaussian_blur (GaussianBlur)   tests/test_latent_transport.py:35
 
     otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
     otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
 
-The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the two OT priors,
+The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the OT priors,
 ``soft_cross_entropy``, ``gaussian_blur``).
 ``ConvBlock`` runs its two branches and the training engine's in-place gradient slots through the packed variant of the
 same kernels (``functional.conv_layers``); ``otvae::conv_bn_act`` is the single-layer functional form.
@@ -37,7 +39,7 @@ from ._lib import check, ptr, stream
 __all__ = ["OPS"]
 
 OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior",
-       "soft_cross_entropy", "gaussian_blur")
+       "soft_cross_entropy", "gaussian_blur", "sliced_w2")
 _lib_def = torch.library.Library("otvae", "DEF")
 
 
@@ -379,6 +381,73 @@ def _sk_backward(ctx, g, _gpi, _giters):
 
 
 torch.library.register_autograd("otvae::sinkhorn_prior", _sk_backward, setup_context=_sk_setup)
+
+
+# ------------------------------------------------------------------------------------------------ sliced W2 prior
+def _sw_fwd(z: Tensor, y: Tensor, dirs: Tensor, scale: float):
+    lib = _lib.load()
+    _lib.require_cuda(z, "latents")
+    if z.dtype != torch.float32:
+        raise NotImplementedError(f"sliced_w2 computes in float32, got {z.dtype} latents")
+    if z.dim() != 2 or y.dim() != 2 or dirs.dim() != 2:
+        raise ValueError(f"sliced_w2 takes z [N, D], y [N, D], dirs [L, D]; got {tuple(z.shape)}, {tuple(y.shape)}, {tuple(dirs.shape)}")
+    n, d = z.shape
+    if tuple(y.shape) != (n, d):
+        raise ValueError(f"prior samples are {tuple(y.shape)}, latents {(n, d)}: sliced_w2 pairs sorted projections one to one")
+    if dirs.shape[1] != d or dirs.shape[0] < 1:
+        raise ValueError(f"projection directions are {tuple(dirs.shape)}, expected [L >= 1, {d}]")
+    z, y, dirs = z.contiguous(), y.to(z.dtype).contiguous(), dirs.to(z.dtype).contiguous()
+    nl = dirs.shape[0]
+    nbytes = lib.otvae_sliced_w2_ws(n, nl)
+    if nbytes < 0:
+        raise NotImplementedError(f"sliced_w2 sorts 1 <= N <= 4096 rows per projection in LDS, got N = {n}")
+    ws = torch.empty(nbytes, device=z.device, dtype=torch.uint8)
+    loss = torch.empty(n, device=z.device, dtype=torch.float32)   # one entry per sample
+    resid = torch.empty((nl, n), device=z.device, dtype=torch.float32)
+    theta = torch.empty((nl, d), device=z.device, dtype=torch.float32)
+    check(lib.otvae_sliced_w2_fwd(ptr(z), ptr(y), ptr(dirs), n, d, nl, float(scale), n, ptr(ws), ptr(theta), ptr(resid), ptr(loss),
+                                  stream()), "otvae_sliced_w2_fwd")
+    return loss, resid, theta
+
+
+def _sw_bwd(g: Tensor, gadd: Optional[Tensor], resid: Tensor, theta: Tensor, scale: float):
+    nl, n = resid.shape
+    d = theta.shape[1]
+    gz = torch.empty((n, d), device=resid.device, dtype=torch.float32)
+    gadd = gadd.contiguous() if gadd is not None else None
+    check(_lib.load().otvae_sliced_w2_bwd(ptr(g.float().contiguous()), ptr(gadd), ptr(resid.contiguous()), ptr(theta.contiguous()), n, d, nl,
+                                          float(scale), ptr(gz), stream()), "otvae_sliced_w2_bwd")
+    return gz
+
+
+_define("sliced_w2", "(Tensor z, Tensor y, Tensor dirs, float scale) -> (Tensor, Tensor, Tensor)", _sw_fwd,
+        lambda z, y, dirs, scale: (z.new_empty(z.shape[0]), z.new_empty(dirs.shape[0], z.shape[0]), z.new_empty(dirs.shape[0], z.shape[1])))
+_define("sliced_w2_backward", "(Tensor g, Tensor? gadd, Tensor resid, Tensor theta, float scale) -> Tensor", _sw_bwd,
+        lambda g, gadd, resid, theta, scale: resid.new_empty(resid.shape[1], theta.shape[1]))
+
+
+def _sw_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1], output[2])
+    ctx.scale = inputs[3]
+    ctx.set_materialize_grads(False)   # resid / theta never carry a gradient
+
+
+def _sw_backward(ctx, g, _gresid, _gtheta):
+    if g is None:
+        return None, None, None, None
+    resid, theta = ctx.saved_tensors
+    return torch.ops.otvae.sliced_w2_backward(g, None, resid, theta, ctx.scale), None, None, None
+
+
+torch.library.register_autograd("otvae::sliced_w2", _sw_backward, setup_context=_sw_setup)
+
+
+def _sw_backward_twice(ctx, g):
+    raise NotImplementedError("otvae::sliced_w2_backward has no derivative of its own: the sliced W2 prior is differentiable once")
+
+
+# an Autograd kernel for the backward op too: differentiating it twice is refused aloud instead of returning a silent constant
+torch.library.register_autograd("otvae::sliced_w2_backward", _sw_backward_twice, setup_context=lambda ctx, inputs, output: None)
 
 
 # ------------------------------------------------------------------------------------------------ Gaussian W2 prior

@@ -2,7 +2,8 @@
 ``sinkhorn_log`` (:276-319), ``w2_gaussian`` (:40-80), ``compute_transport_operators`` (:391-458, eq. 17),
 ``apply_transport`` (:464-527), ``batch_w2_dissimilarity_gaussian_diag`` (:86-134), ``W2Mixin`` (:533-600).
 Out of scope for this path: GMM transport (``batch_ot_gmm``), barycenters, the stochastic
-(eq. 19) operators -- they raise ``NotImplementedError``."""
+(eq. 19) operators -- they raise ``NotImplementedError``.
+``sliced_w2`` has no counterpart in the reference: the sliced Wasserstein-2 distance behind ``prior.SlicedWassersteinPrior``."""
 import math
 import warnings
 from functools import partial
@@ -18,7 +19,7 @@ from .matrix_utils import *  # noqa: F401,F403
 from .matrix_utils import (STABILITY_CONST, cholesky, pinv_sym, spectral_fn, eigh_vectors, eigvals_and_fn, eye_like, is_symmetric, matmul64, mean_cov, psd_shift,
                            spectral_fn)
 
-__all__ = ["w2_gaussian", "batch_w2_dissimilarity_gaussian_diag", "batch_w2_dissimilarity_gaussian", "gaussian_barycenter", "batch_ot_gmm", "sinkhorn_log", "sinkhorn_log_potentials",
+__all__ = ["w2_gaussian", "batch_w2_dissimilarity_gaussian_diag", "batch_w2_dissimilarity_gaussian", "gaussian_barycenter", "batch_ot_gmm", "sinkhorn_log", "sinkhorn_log_potentials", "sliced_w2",
            "sq_euclidean_cost", "ot_cost", "compute_transport_operators", "apply_transport", "W2Mixin"]
 
 _DT = {torch.float32: 0, torch.float64: 1}
@@ -131,6 +132,32 @@ def sinkhorn_log(a: Tensor, b: Tensor, C: Tensor, reg: float = 1e-5, max_iter: i
         pi = _SinkhornLogFn.apply(a2, b2, C.reshape(-1, n, m).contiguous(), reg, max_iter, threshold)
         return pi.reshape(*lead, n, m)
     return sinkhorn_log_potentials(a, b, C, reg, max_iter, threshold)[0]
+
+
+def sliced_w2(z: Tensor, y: Tensor, n_projections: int = 128, projections: Optional[Tensor] = None, seed: Optional[int] = None,
+              key: Optional[Tensor] = None) -> Tensor:
+    """Sliced Wasserstein-2 between two samples of equal size: z [N, D], y [N, D] (float32) -> the scalar
+    1 / (L N) sum_l sum_k (p_l,(k) - q_l,(k))^2 with p = z theta^T, q = y theta^T sorted per direction (ties: the smaller row first) and
+    theta_l = g_l / |g_l|.  ``projections`` are the raw directions g [L, D]; without them ``n_projections`` standard-normal rows are
+    drawn on the device under ``key`` (``functional.new_rng_key``; a fresh key from ``seed`` when absent).  1 <= N <= 4096 (one
+    workgroup sorts a projection in LDS); beyond it ``NotImplementedError``.
+
+    Differentiable in ``z`` (``otvae::sliced_w2`` / ``otvae::sliced_w2_backward``): the gradient 2 / (L N) sum_l r_l,i theta_l is exact,
+    the rank matching being piecewise constant.  ``y`` and the directions get no gradient."""
+    from .. import functional as HF
+    if z.dim() != 2 or tuple(y.shape) != tuple(z.shape):
+        raise ValueError(f"sliced_w2: z {tuple(z.shape)} and y {tuple(y.shape)} must both be [N, D]")
+    if projections is None:
+        if isinstance(n_projections, bool) or not isinstance(n_projections, int) or n_projections < 1:
+            raise ValueError(f"sliced_w2: n_projections must be a positive integer, got {n_projections!r}")
+    elif projections.dim() != 2 or projections.shape[1] != z.shape[1] or projections.shape[0] < 1:
+        raise ValueError(f"sliced_w2: projections are {tuple(projections.shape)}, expected [L, {z.shape[1]}]")
+    _lib.require_cuda(z, "z")
+    if projections is None:
+        if key is None:
+            key = HF.new_rng_key(z.device, seed)
+        projections = HF.normal_fill_(torch.empty((n_projections, z.shape[1]), device=z.device, dtype=torch.float32), key, stream_id=2)
+    return torch.ops.otvae.sliced_w2(z, y.detach(), projections.detach(), 1.0)[0][0]
 
 
 class _SqEuclideanCostFn(torch.autograd.Function):
