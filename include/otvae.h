@@ -36,7 +36,8 @@ int otvae_stream_create(void** stream);
 int otvae_stream_destroy(void* stream);
 
 /* Geometry of one ConvLayer (networks/cnn.py:48-154,183-192): input [N][Hs][Ws][Cs] --(nearest x`up`)-->
- * conv KHxKW / stride / pad --> [N][Ho][Wo][Cn].  `up` is 1 or 2; up==2 requires stride==1. */
+ * conv KHxKW / stride / pad --> [N][Ho][Wo][Cn].  `up` is 1 or 2; up==2 requires stride==1.  pad >= 0 and Ho, Wo > 0:
+ * a negative padding or an empty output is OTVAE_EINVAL. */
 typedef struct {
     int32_t N, Hs, Ws, Cs;
     int32_t up;

@@ -34,6 +34,8 @@ static int check_geom(const otvae_conv_geom* g, const char* who) {
     OTVAE_REQUIRE(g->stride == 1 || g->stride == 2, "%s: stride must be 1 or 2 (got %d)", who, g->stride);
     OTVAE_REQUIRE(!(g->up == 2 && g->stride != 1), "%s: up-sampling with stride != 1 unsupported", who);
     OTVAE_REQUIRE(g->KH >= 1 && g->KH <= 7 && g->KW >= 1 && g->KW <= 7, "%s: kernel size out of range", who);
+    OTVAE_REQUIRE(g->pad >= 0, "%s: negative padding (got %d)", who, g->pad);
+    OTVAE_REQUIRE(g->Ho > 0 && g->Wo > 0, "%s: empty output %dx%d (kernel larger than the padded input)", who, g->Ho, g->Wo);
     int Hu = g->Hs * g->up, Wu = g->Ws * g->up;
     int ho = (Hu + 2 * g->pad - g->KH) / g->stride + 1, wo = (Wu + 2 * g->pad - g->KW) / g->stride + 1;
     OTVAE_REQUIRE(ho == g->Ho && wo == g->Wo, "%s: output size mismatch: geom says %dx%d, conv gives %dx%d", who,

@@ -41,17 +41,27 @@ def raw(t):  # the NHWC memory as a plain contiguous [N, H, W, C] tensor
     return t.permute(0, 2, 3, 1)
 
 
-def make_case(n, cs, cn, hs, k, stride, pad, up, norm=True, relu=True, bias=True, res=True, seed=0):
+def make_case(n, cs, cn, hs, k, stride, pad, up, norm=True, relu=True, bias=True, res=True, seed=0, ws=None, kw=None):
+    """``ws`` / ``kw``: width of the map / of the kernel when it differs from the height ``hs`` / ``k``."""
+    ws = hs if ws is None else ws
+    kw = k if kw is None else kw
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, cs, hs, hs, generator=g)
-    w = torch.randn(cn, cs, k, k, generator=g) * (1.0 / (k * k * cs) ** 0.5)
+    x = torch.randn(n, cs, hs, ws, generator=g)
+    w = torch.randn(cn, cs, k, kw, generator=g) * (1.0 / (k * kw * cs) ** 0.5)
     scale = torch.rand(cs, generator=g) + 0.5 if norm else None
     shift = torch.randn(cs, generator=g) * 0.3 if norm else None
     b = torch.randn(cn, generator=g) if bias else None
     ho = (hs * up + 2 * pad - k) // stride + 1
-    r = torch.randn(n, cn, ho, ho, generator=g) if res else None
-    gy = torch.randn(n, cn, ho, ho, generator=g)
-    return dict(x=x, w=w, scale=scale, shift=shift, bias=b, res=r, gy=gy, stride=stride, pad=pad, up=up, relu=relu, ho=ho)
+    wo = (ws * up + 2 * pad - kw) // stride + 1
+    r = torch.randn(n, cn, ho, wo, generator=g) if res else None
+    gy = torch.randn(n, cn, ho, wo, generator=g)
+    return dict(x=x, w=w, scale=scale, shift=shift, bias=b, res=r, gy=gy, stride=stride, pad=pad, up=up, relu=relu, ho=ho, wo=wo)
+
+
+def make_case2(case, **flags):
+    """make_case from a two-axis tuple (n, cs, cn, hs, ws, kh, kw, stride, pad, up)."""
+    n, cs, cn, hs, ws, kh, kw, stride, pad, up = case
+    return make_case(n, cs, cn, hs, kh, stride, pad, up, ws=ws, kw=kw, **flags)
 
 
 def ref64(c):
@@ -88,12 +98,12 @@ class Dev:
         self.scale = c["scale"].to(d) if c["scale"] is not None else None
         self.shift = c["shift"].to(d) if c["shift"] is not None else None
         self.bias = c["bias"].to(d) if c["bias"] is not None else None
-        n, cs, hs, _ = c["x"].shape
-        cn, _, k, _ = c["w"].shape
-        self.geom = L.ConvGeom(n, hs, hs, cs, c["up"], c["ho"], c["ho"], cn, k, k, c["stride"], c["pad"])
-        self.n, self.cs, self.cn, self.hs, self.k = n, cs, cn, hs, k
-        self.wd = torch.empty(k * k * cn * cs, device=d)
-        assert load().otvae_weight_transpose(L.ptr(self.w_hwio), L.ptr(self.wd), k * k, cs, cn, L.stream()) == 0
+        n, cs, hs, ws = c["x"].shape
+        cn, _, k, kw = c["w"].shape
+        self.geom = L.ConvGeom(n, hs, ws, cs, c["up"], c["ho"], c["wo"], cn, k, kw, c["stride"], c["pad"])
+        self.n, self.cs, self.cn, self.hs, self.ws, self.k, self.kw = n, cs, cn, hs, ws, k, kw
+        self.wd = torch.empty(k * kw * cn * cs, device=d)
+        assert load().otvae_weight_transpose(L.ptr(self.w_hwio), L.ptr(self.wd), k * kw, cs, cn, L.stream()) == 0
 
 
 def load():
@@ -102,7 +112,7 @@ def load():
 
 def run_fwd(dv, stats=True):
     L, lib = _L(), load()
-    y = nhwc(torch.empty(dv.n, dv.cn, dv.c["ho"], dv.c["ho"], device="cuda"))
+    y = nhwc(torch.empty(dv.n, dv.cn, dv.c["ho"], dv.c["wo"], device="cuda"))
     part = None
     p, ld = C.c_int(0), C.c_int(0)
     if stats:
@@ -117,7 +127,7 @@ def run_fwd(dv, stats=True):
 
 def run_dgrad(dv, sums=True):
     L, lib = _L(), load()
-    gv = nhwc(torch.empty(dv.n, dv.cs, dv.hs, dv.hs, device="cuda"))
+    gv = nhwc(torch.empty(dv.n, dv.cs, dv.hs, dv.ws, device="cuda"))
     p, cp = C.c_int(0), C.c_int(0)
     L.check(lib.otvae_conv_bwd_data_ws(C.byref(dv.geom), C.byref(p), C.byref(cp)), "ws")
     mean = torch.linspace(-0.2, 0.2, dv.cs, device="cuda") if sums else None
@@ -134,7 +144,7 @@ def run_wgrad(dv):
     p = C.c_int(0)
     has_bias = dv.bias is not None
     L.check(lib.otvae_conv_bwd_weight_ws(C.byref(dv.geom), int(has_bias), C.byref(p)), "ws")
-    kk = dv.k * dv.k * dv.cs + (1 if has_bias else 0)
+    kk = dv.k * dv.kw * dv.cs + (1 if has_bias else 0)
     part = torch.empty((p.value, kk, dv.cn), device="cuda")
     gw = torch.empty_like(dv.w_hwio)
     gb = torch.empty(dv.cn, device="cuda") if has_bias else None
@@ -301,31 +311,36 @@ def test_conv_multi_equals_single_calls(lib):
             assert torch.equal(part[:, :dv.cs].sum(-1), singles[i][5])
 
 
-@pytest.mark.parametrize("shape", [(64, 256, 256, 1, 3, 1, 1, 1), (64, 64, 128, 2, 4, 2, 1, 1), (64, 32, 64, 2, 3, 1, 1, 1)],
-                         ids=["3x3_on_1x1", "4x4s2_2x2_to_1x1", "3x3_on_2x2_no_dead_tap"])
+# 8 entries: (n, cs, cn, hs, k, stride, pad, up), square; 10 entries: (n, cs, cn, hs, ws, kh, kw, stride, pad, up)
+@pytest.mark.parametrize("shape", [(64, 256, 256, 1, 3, 1, 1, 1), (64, 64, 128, 2, 4, 2, 1, 1), (64, 32, 64, 2, 3, 1, 1, 1),
+                                   (37, 32, 32, 1, 4, 3, 3, 1, 1, 1), (37, 32, 32, 4, 1, 3, 3, 1, 1, 1),
+                                   (33, 64, 128, 2, 6, 4, 4, 2, 1, 1)],
+                         ids=["3x3_on_1x1", "4x4s2_2x2_to_1x1", "3x3_on_2x2_no_dead_tap", "3x3_on_1x4", "3x3_on_4x1", "4x4s2_2x6_to_1x3"])
 def test_deferred_sparse_reduce_skips_dead_taps(lib, shape):
     """Layers whose map is smaller than the kernel: the taps that never touch the image have a zero gradient.  With
     defer_reduce = OTVAE_DEFER_SPARSE the kernels may leave those partial rows unwritten (the workspace is pre-filled with
     NaN here) and otvae_wgrad_reduce_batched, given the mask of otvae_conv_dead_taps, must produce exactly the gradient of
     the immediate (dense) path."""
     L = _L()
-    n, cs, cn, hs, k, s, p, up = shape
-    dv = Dev(make_case(n, cs, cn, hs, k, s, p, up, seed=11))
+    if len(shape) == 8:
+        shape = shape[:4] + (shape[3], shape[4]) + shape[4:]
+    n, cs, cn, hs, ws, k, kw_, s, p, up = shape
+    dv = Dev(make_case(n, cs, cn, hs, k, s, p, up, seed=11, ws=ws, kw=kw_))
     gw_ref, gb_ref = run_wgrad(dv)
     dead = C.c_uint32(0)
     L.check(lib.otvae_conv_dead_taps(C.byref(dv.geom), C.byref(dead)), "dead taps")
-    ho = dv.c["ho"]
+    ho, wo = dv.c["ho"], dv.c["wo"]
     expect = 0
     for kh in range(k):
-        for kw in range(k):
-            touch = lambda d: (d + (ho - 1) * s >= 0) and (d < hs * up)  # noqa: E731
-            if not (touch(kh - p) and touch(kw - p)):
-                expect |= 1 << (kh * k + kw)
+        for kw in range(kw_):
+            touch = lambda d, o, size: (d + (o - 1) * s >= 0) and (d < size * up)  # noqa: E731
+            if not (touch(kh - p, ho, hs) and touch(kw - p, wo, ws)):
+                expect |= 1 << (kh * kw_ + kw)
     assert dead.value == expect
     has_bias = dv.bias is not None
     pw = C.c_int(0)
     L.check(lib.otvae_conv_bwd_weight_ws(C.byref(dv.geom), int(has_bias), C.byref(pw)), "ws")
-    kk = k * k * cs + (1 if has_bias else 0)
+    kk = k * kw_ * cs + (1 if has_bias else 0)
     wpart = torch.full((pw.value, kk, cn), float("nan"), device="cuda")
     gw = torch.full_like(dv.w_hwio, float("nan"))
     gb = torch.full((cn,), float("nan"), device="cuda") if has_bias else None
@@ -344,8 +359,8 @@ def test_deferred_sparse_reduce_skips_dead_taps(lib, shape):
     if has_bias:
         assert torch.equal(gb, gb_ref)
     if dead.value:
-        g4 = gw.reshape(k * k, cs, cn)
-        for t in range(k * k):
+        g4 = gw.reshape(k * kw_, cs, cn)
+        for t in range(k * kw_):
             if (dead.value >> t) & 1:
                 assert not g4[t].any()
         assert torch.isnan(wpart).any()      # the kernels really skipped the dead rows

@@ -48,13 +48,13 @@ def prepared(case, **flags):
     return _cache[key]
 
 
-def nan_nhwc(n, ch, h):
-    return T.nhwc(torch.full((n, ch, h, h), float("nan"), device="cuda"))
+def nan_nhwc(n, ch, h, w=None):
+    return T.nhwc(torch.full((n, ch, h, h if w is None else w), float("nan"), device="cuda"))
 
 
 def fwd(dv):
     L, lib = T._L(), T.load()
-    y = nan_nhwc(dv.n, dv.cn, dv.c["ho"])
+    y = nan_nhwc(dv.n, dv.cn, dv.c["ho"], dv.c["wo"])
     p, ld = C.c_int(0), C.c_int(0)
     L.check(lib.otvae_conv_fwd_stats_ws(C.byref(dv.geom), C.byref(p), C.byref(ld)), "ws")
     part = torch.full((2, ld.value, p.value), float("nan"), device="cuda", dtype=torch.float64)
@@ -66,7 +66,7 @@ def fwd(dv):
 
 def dgrad(dv):
     L, lib = T._L(), T.load()
-    gv = nan_nhwc(dv.n, dv.cs, dv.hs)
+    gv = nan_nhwc(dv.n, dv.cs, dv.hs, dv.ws)
     p, cp = C.c_int(0), C.c_int(0)
     L.check(lib.otvae_conv_bwd_data_ws(C.byref(dv.geom), C.byref(p), C.byref(cp)), "ws")
     mean = torch.linspace(-0.2, 0.2, dv.cs, device="cuda")
@@ -148,14 +148,18 @@ def test_host_count_sees_what_the_test_cases_exercise():
 
 
 # (e) packed two-branch calls: (branch a, branch b) read the same input
+# (8 entries: square, the tuple of CASES; 10 entries: (n, cs, cn, hs, ws, kh, kw, stride, pad, up))
 MULTI = [((70, 64, 64, 2, 3, 1, 1, 1), (70, 64, 64, 2, 1, 1, 0, 1)),
-         ((21, 32, 64, 4, 4, 2, 1, 1), (21, 32, 64, 4, 4, 2, 1, 1))]
+         ((21, 32, 64, 4, 4, 2, 1, 1), (21, 32, 64, 4, 4, 2, 1, 1)),
+         ((70, 64, 64, 2, 3, 3, 3, 1, 1, 1), (70, 64, 64, 2, 3, 1, 1, 1, 0, 1)),
+         ((21, 32, 64, 4, 6, 4, 4, 2, 1, 1), (21, 32, 64, 4, 6, 4, 4, 2, 1, 1))]
 
 
-@pytest.mark.parametrize("pair", MULTI, ids=["3x3_with_1x1_at_2x2", "two_4x4s2_at_4x4"])
+@pytest.mark.parametrize("pair", MULTI, ids=["3x3_with_1x1_at_2x2", "two_4x4s2_at_4x4", "3x3_with_1x1_at_2x3", "two_4x4s2_at_4x6"])
 def test_packed_two_branch_calls_equal_single_calls(pair):
     L, lib = T._L(), T.load()
-    dvs = [T.Dev(T.make_case(*pair[0], seed=5)), T.Dev(T.make_case(*pair[1], bias=False, seed=6))]
+    mk = lambda case, **kw: T.make_case(*case, **kw) if len(case) == 8 else T.make_case2(case, **kw)  # noqa: E731
+    dvs = [T.Dev(mk(pair[0], seed=5)), T.Dev(mk(pair[1], bias=False, seed=6))]
     dvs[1].x = dvs[0].x
     singles = []
     for dv in dvs:
@@ -170,7 +174,7 @@ def test_packed_two_branch_calls_equal_single_calls(pair):
         p, ld = C.c_int(0), C.c_int(0)
         L.check(lib.otvae_conv_fwd_stats_ws(C.byref(dv.geom), C.byref(p), C.byref(ld)), "ws")
         part = torch.full((2, ld.value, p.value), float("nan"), device="cuda", dtype=torch.float64)
-        y = nan_nhwc(dv.n, dv.cn, dv.c["ho"])
+        y = nan_nhwc(dv.n, dv.cn, dv.c["ho"], dv.c["wo"])
         jb.kind, jb.relu, jb.geom = L.JOB_FWD, int(dv.c["relu"]), dv.geom
         jb.x, jb.scale, jb.shift, jb.w = L.ptr(dv.x), L.ptr(dv.scale), L.ptr(dv.shift), L.ptr(dv.w_hwio)
         jb.bias, jb.residual, jb.y, jb.stat_partial = L.ptr(dv.bias), L.ptr(dv.res), L.ptr(y), L.ptr(part)
@@ -188,7 +192,7 @@ def test_packed_two_branch_calls_equal_single_calls(pair):
     for jb, dv in zip(jobs, dvs):
         pd, cp = C.c_int(0), C.c_int(0)
         L.check(lib.otvae_conv_bwd_data_ws(C.byref(dv.geom), C.byref(pd), C.byref(cp)), "ws")
-        gv = nan_nhwc(dv.n, dv.cs, dv.hs)
+        gv = nan_nhwc(dv.n, dv.cs, dv.hs, dv.ws)
         mean = torch.linspace(-0.2, 0.2, dv.cs, device="cuda")
         invstd = torch.linspace(0.8, 1.2, dv.cs, device="cuda")
         part = torch.full((2, cp.value, pd.value), float("nan"), device="cuda", dtype=torch.float64)
