@@ -557,6 +557,29 @@ int otvae_sliced_w2_fwd(const float* z, const float* y, const float* dirs, int N
 int otvae_sliced_w2_bwd(const float* gout, const float* gadd, const float* resid, const float* theta, int N, int D, int L,
                         double scale, float* gz, void* stream);
 
+/* ---- kernel two-sample (MMD) loss between latents and prior draws (MMDPrior; SURVEY F3: no reference class) ------------- */
+/* z[N][D], y[M][D], fp32.  r(a, b) = |a - b|^2 (Gram form on the fp32 matrix cores, clamped below at 0, NaN passes the clamp),
+ * C_k = 2 D sigma2 scales[k], k = 0 .. nscales - 1 <= 8 (scales: HOST array, read at launch time);
+ *   kernel 0 (imq): k(r) = sum_k C_k / (C_k + r),   w(r) = -k'(r) = sum_k C_k / (C_k + r)^2
+ *   kernel 1 (rbf): k(r) = sum_k exp(-r / C_k),     w(r) = sum_k exp(-r / C_k) / C_k
+ *   Ezz = cz sum_{i != j} k(r(z_i, z_j)), Eyy = cy sum_{i != j} k(r(y_i, y_j)), Ezy = 1 / (N M) sum_{i, j} k(r(z_i, y_j)),
+ *   cz = 1 / (N (N - 1)), cy = 1 / (M (M - 1)) (unbiased != 0; needs N, M >= 2) or 1 / N^2, 1 / M^2 with the diagonal k(0) in the sums
+ *   (unbiased == 0).  The diagonal is identified by INDEX: two different rows holding the same vector are a pair.
+ *   loss[loss_rep] = scale (Ezz + Eyy - 2 Ezy), the same value loss_rep times; terms[3] = (Ezz, Eyy, Ezy), unscaled;
+ *   G[N][D] (may be NULL: then the gradient product is skipped) = scale d MMD2 / d z,
+ *   d MMD2 / d z_i = -4 cz sum_{j != i} w(r(z_i, z_j)) (z_i - z_j) + 4 / (N M) sum_j w(r(z_i, y_j)) (z_i - y_j).
+ * One main launch (a workgroup takes a 32-row tile against a run of 32-row column tiles: Gram tile, k and w, w re-laid through LDS
+ * into the A operand of a second product with the staged column rows) and a finishing launch that adds the fp64 partial sums of k
+ * and the partial gradient tiles of the column splits in index order: bit-reproducible, no float atomic, nothing of size N x M in
+ * memory.  ws: otvae_mmd_ws bytes, 16-byte aligned, written before it is read.  A latent or draw that is not finite makes the loss NaN.
+ * Envelope: 1 <= D <= 512, N D and M D below 2^31; beyond it OTVAE_EUNSUPPORTED (otvae_mmd_ws: -1). */
+int64_t otvae_mmd_ws(int N, int M, int D);
+int otvae_mmd_fwd(const float* z, const float* y, int N, int M, int D, int kernel, const double* scales, int nscales, double sigma2,
+                  int unbiased, double scale, int loss_rep, void* ws, float* loss, float* terms, float* G, void* stream);
+/* gz[i][d] = (gadd ? gadd[i][d] : 0) + (sum_b gout[b]) G[i][d]; gout[ng] are the upstream gradients of the loss replicas, gadd[N][D]
+ * (may be NULL) the gradient reaching z through its other consumer.  One launch; the product is rounded before the single fp32 add. */
+int otvae_mmd_bwd(const float* gout, int ng, const float* gadd, const float* G, int N, int D, float* gz, void* stream);
+
 /* ---- Gaussian W2 with empirical covariance as a loss term (GaussianW2Prior; BASELINE north_star) ------------ */
 /* Forward tail of L = w2_gaussian(mean_cov(_stats(z)), N(mut, covt)) (ot/w2_utils.py:40-80, ot/matrix_utils.py:145-158,
  * gaussian_model.py:144-157): lam[D], vt[D][D] = eigenvalues / eigenvector rows of M = covt^1/2 cov covt^1/2 (otvae_eigh_fn,

@@ -22,6 +22,7 @@ pi32 = C.POINTER(C.c_int)
 pu32 = C.POINTER(C.c_uint32)
 pi64 = C.POINTER(C.c_int64)
 pf32 = C.POINTER(C.c_float)  # host array of floats
+pf64 = C.POINTER(C.c_double)  # host array of doubles
 
 
 class ConvGeom(C.Structure):
@@ -156,6 +157,9 @@ SIGNATURES = {
     "otvae_sliced_w2_ws": (i64, [i32, i32]),
     "otvae_sliced_w2_fwd": (i32, [vp, vp, vp, i32, i32, i32, f64, i32, vp, vp, vp, vp, vp]),
     "otvae_sliced_w2_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f64, vp, vp]),
+    "otvae_mmd_ws": (i64, [i32, i32, i32]),
+    "otvae_mmd_fwd": (i32, [vp, vp, i32, i32, i32, i32, pf64, i32, f64, i32, f64, i32, vp, vp, vp, vp, vp]),
+    "otvae_mmd_bwd": (i32, [vp, i32, vp, vp, i32, i32, vp, vp]),
     "otvae_w2_prior_tail": (i32, [vp, vp, vp, vp, vp, vp, i32, f64, i32, vp, vp, vp]),
     "otvae_w2_prior_bwd": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, i32, f64, vp, vp, vp]),
     "otvae_gauss_stats_ws": (i64, [i32, i32, i32, i32]),

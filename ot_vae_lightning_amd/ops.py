@@ -13,6 +13,8 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
                                                                                  w2_utils.py:40-80
     otvae::sliced_w2                sliced Wasserstein-2 (sort and match per     no reference class (SURVEY.md F3)
                                     projection)
+    otvae::mmd_prior                kernel two-sample (MMD) loss and its latent  no reference class (SURVEY.md F3)
+                                    gradient, one fused launch
     otvae::soft_cross_entropy       DAD.prior_loss's shifted soft-label CE       model/discrete_auto_diffuser.py:63-72
     otvae::gaussian_blur            torchvision's gaussian_blur (GaussianBlur)   tests/test_latent_transport.py:35
 
@@ -39,7 +41,7 @@ from ._lib import check, ptr, stream
 __all__ = ["OPS"]
 
 OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior",
-       "soft_cross_entropy", "gaussian_blur", "sliced_w2")
+       "soft_cross_entropy", "gaussian_blur", "sliced_w2", "mmd_prior")
 _lib_def = torch.library.Library("otvae", "DEF")
 
 
@@ -448,6 +450,115 @@ def _sw_backward_twice(ctx, g):
 
 # an Autograd kernel for the backward op too: differentiating it twice is refused aloud instead of returning a silent constant
 torch.library.register_autograd("otvae::sliced_w2_backward", _sw_backward_twice, setup_context=lambda ctx, inputs, output: None)
+
+
+# ------------------------------------------------------------------------------------------------ MMD prior
+MMD_KERNELS = {"imq": 0, "rbf": 1}
+MMD_MAX_SCALES = 8
+MMD_MAX_D = 512   # csrc/mmd.hip: the gradient accumulators of a 32-row tile stay in registers, both staged tiles in LDS
+
+
+def mmd_kernel_id(kernel) -> int:
+    if not isinstance(kernel, str) or kernel not in MMD_KERNELS:
+        raise ValueError(f"mmd: unknown kernel {kernel!r}, expected one of {sorted(MMD_KERNELS)}")
+    return MMD_KERNELS[kernel]
+
+
+def mmd_check_config(scales, sigma2) -> Tuple[float, ...]:
+    """the scales as a tuple of floats; ValueError for none, more than 8, a non-positive one or a non-positive sigma2"""
+    try:
+        scales = tuple(float(s) for s in scales)
+    except TypeError:
+        raise ValueError(f"mmd: scales must be a sequence of positive numbers, got {scales!r}") from None
+    if not 1 <= len(scales) <= MMD_MAX_SCALES:
+        raise ValueError(f"mmd: 1 to {MMD_MAX_SCALES} scales, got {len(scales)}")
+    if not all(s > 0 and s == s and s != float("inf") for s in scales):
+        raise ValueError(f"mmd: every scale must be positive and finite, got {scales}")
+    if not (float(sigma2) > 0 and float(sigma2) != float("inf")):
+        raise ValueError(f"mmd: sigma2 must be positive and finite, got {sigma2!r}")
+    return scales
+
+
+def mmd_check_inputs(z: Tensor, y: Tensor, unbiased: bool) -> None:
+    """the shape / dtype refusals of ``otvae::mmd_prior``, before any kernel (also called by ``MMDPrior`` and ``ot.mmd2``)"""
+    if z.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"mmd takes z [N, D] and y [M, D]; got {tuple(z.shape)}, {tuple(y.shape)}")
+    if y.shape[1] != z.shape[1]:
+        raise ValueError(f"mmd: prior samples are {tuple(y.shape)}, latents {tuple(z.shape)}: the widths D differ")
+    least = 2 if unbiased else 1
+    if z.shape[0] < least or y.shape[0] < least or z.shape[1] < 1:
+        raise ValueError(f"mmd: the {'unbiased' if unbiased else 'biased'} estimator needs N, M >= {least} and D >= 1, got N = "
+                         f"{z.shape[0]}, M = {y.shape[0]}, D = {z.shape[1]}")
+    if z.dtype != torch.float32:
+        raise NotImplementedError(f"mmd computes in float32, got {z.dtype} latents")
+
+
+def _mmd_fwd(z: Tensor, y: Tensor, kernel: int, scales, sigma2: float, unbiased: bool, scale: float, need_grad: bool):
+    if kernel not in (0, 1):
+        raise ValueError(f"mmd: kernel id must be 0 (imq) or 1 (rbf), got {kernel}")
+    scales = mmd_check_config(scales, sigma2)
+    mmd_check_inputs(z, y, unbiased)
+    _lib.require_cuda(z, "latents")
+    lib = _lib.load()
+    n, d = z.shape
+    m = y.shape[0]
+    nbytes = lib.otvae_mmd_ws(n, m, d)
+    if nbytes < 0:
+        raise NotImplementedError(f"mmd_prior is built for 1 <= D <= {MMD_MAX_D} (N D, M D below 2^31), got N = {n}, M = {m}, D = {d}")
+    z, y = z.contiguous(), y.to(z.dtype).contiguous()
+    ws = torch.empty(nbytes, device=z.device, dtype=torch.uint8)
+    loss = torch.empty(n, device=z.device, dtype=torch.float32)   # one entry per sample
+    terms = torch.empty(3, device=z.device, dtype=torch.float32)
+    G = torch.empty((n if need_grad else 0, d), device=z.device, dtype=torch.float32)
+    sc = (C.c_double * len(scales))(*scales)   # read by the call itself: a captured graph holds the constants by value
+    check(lib.otvae_mmd_fwd(ptr(z), ptr(y), n, m, d, int(kernel), sc, len(scales), float(sigma2), int(bool(unbiased)), float(scale), n,
+                            ptr(ws), ptr(loss), ptr(terms), ptr(G) if need_grad else None, stream()), "otvae_mmd_fwd")
+    return loss, G, terms
+
+
+def _mmd_bwd(g: Tensor, gadd: Optional[Tensor], G: Tensor):
+    n, d = G.shape
+    if n < 1:
+        raise ValueError("mmd_prior_backward: the forward ran with need_grad=False and kept no gradient")
+    gz = torch.empty((n, d), device=G.device, dtype=torch.float32)
+    g = g.float().contiguous()
+    gadd = gadd.contiguous() if gadd is not None else None
+    check(_lib.load().otvae_mmd_bwd(ptr(g), g.numel(), ptr(gadd), ptr(G.contiguous()), n, d, ptr(gz), stream()), "otvae_mmd_bwd")
+    return gz
+
+
+_define("mmd_prior", "(Tensor z, Tensor y, int kernel, float[] scales, float sigma2, bool unbiased, float scale, bool need_grad) -> "
+        "(Tensor, Tensor, Tensor)", _mmd_fwd,
+        lambda z, y, kernel, scales, sigma2, unbiased, scale, need_grad: (z.new_empty(z.shape[0]),
+                                                                          z.new_empty(z.shape[0] if need_grad else 0, z.shape[1]),
+                                                                          z.new_empty(3)))
+_define("mmd_prior_backward", "(Tensor g, Tensor? gadd, Tensor G) -> Tensor", _mmd_bwd, lambda g, gadd, G: G.new_empty(G.shape))
+
+
+def _mmd_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.need_grad = inputs[7]
+    ctx.set_materialize_grads(False)   # G / terms never carry a gradient
+
+
+def _mmd_backward(ctx, g, _gG, _gterms):
+    if g is None:
+        return (None,) * 8
+    if not ctx.need_grad:
+        raise RuntimeError("otvae::mmd_prior ran with need_grad=False: it kept no gradient to propagate")
+    (G,) = ctx.saved_tensors
+    return (torch.ops.otvae.mmd_prior_backward(g, None, G),) + (None,) * 7
+
+
+torch.library.register_autograd("otvae::mmd_prior", _mmd_backward, setup_context=_mmd_setup)
+
+
+def _mmd_backward_twice(ctx, g):
+    raise NotImplementedError("otvae::mmd_prior_backward has no derivative of its own: the MMD prior is differentiable once")
+
+
+# as for the sliced prior: differentiating the backward op is refused aloud instead of returning a silent constant
+torch.library.register_autograd("otvae::mmd_prior_backward", _mmd_backward_twice, setup_context=lambda ctx, inputs, output: None)
 
 
 # ------------------------------------------------------------------------------------------------ Gaussian W2 prior

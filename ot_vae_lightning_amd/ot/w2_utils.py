@@ -3,7 +3,8 @@
 ``apply_transport`` (:464-527), ``batch_w2_dissimilarity_gaussian_diag`` (:86-134), ``W2Mixin`` (:533-600).
 Out of scope for this path: GMM transport (``batch_ot_gmm``), barycenters, the stochastic
 (eq. 19) operators -- they raise ``NotImplementedError``.
-``sliced_w2`` has no counterpart in the reference: the sliced Wasserstein-2 distance behind ``prior.SlicedWassersteinPrior``."""
+``sliced_w2`` has no counterpart in the reference: the sliced Wasserstein-2 distance behind ``prior.SlicedWassersteinPrior``; nor
+has ``mmd2``, the kernel two-sample statistic behind ``prior.MMDPrior``."""
 import math
 import warnings
 from functools import partial
@@ -19,7 +20,7 @@ from .matrix_utils import *  # noqa: F401,F403
 from .matrix_utils import (STABILITY_CONST, cholesky, pinv_sym, spectral_fn, eigh_vectors, eigvals_and_fn, eye_like, is_symmetric, matmul64, mean_cov, psd_shift,
                            spectral_fn)
 
-__all__ = ["w2_gaussian", "batch_w2_dissimilarity_gaussian_diag", "batch_w2_dissimilarity_gaussian", "gaussian_barycenter", "batch_ot_gmm", "sinkhorn_log", "sinkhorn_log_potentials", "sliced_w2",
+__all__ = ["w2_gaussian", "batch_w2_dissimilarity_gaussian_diag", "batch_w2_dissimilarity_gaussian", "gaussian_barycenter", "batch_ot_gmm", "sinkhorn_log", "sinkhorn_log_potentials", "sliced_w2", "mmd2",
            "sq_euclidean_cost", "ot_cost", "compute_transport_operators", "apply_transport", "W2Mixin"]
 
 _DT = {torch.float32: 0, torch.float64: 1}
@@ -158,6 +159,23 @@ def sliced_w2(z: Tensor, y: Tensor, n_projections: int = 128, projections: Optio
             key = HF.new_rng_key(z.device, seed)
         projections = HF.normal_fill_(torch.empty((n_projections, z.shape[1]), device=z.device, dtype=torch.float32), key, stream_id=2)
     return torch.ops.otvae.sliced_w2(z, y.detach(), projections.detach(), 1.0)[0][0]
+
+
+def mmd2(z: Tensor, y: Tensor, kernel: str = "imq", scales=(0.1, 0.2, 0.5, 1.0, 2.0, 5.0, 10.0), sigma2: float = 1.0,
+         unbiased: bool = True) -> Tensor:
+    """Squared maximum mean discrepancy between two samples: z [N, D], y [M, D] (float32, any N against any M) -> the scalar
+    Ezz + Eyy - 2 Ezy for the kernel k(r) = sum_k C_k / (C_k + r) (``"imq"``) or sum_k exp(-r / C_k) (``"rbf"``) of r = |a - b|^2 with
+    C_k = 2 D sigma2 scales[k]; the unbiased estimator leaves the diagonals out (N, M >= 2) and may be negative.  1 <= D <= 512;
+    beyond it ``NotImplementedError``.
+
+    Differentiable in ``z`` (``otvae::mmd_prior`` / ``otvae::mmd_prior_backward``); ``y`` gets no gradient."""
+    from .. import ops
+    kid = ops.mmd_kernel_id(kernel)
+    scales = ops.mmd_check_config(scales, sigma2)
+    ops.mmd_check_inputs(z, y, bool(unbiased))
+    _lib.require_cuda(z, "z")
+    need_grad = bool(torch.is_grad_enabled() and z.requires_grad)
+    return torch.ops.otvae.mmd_prior(z, y.detach(), kid, list(scales), float(sigma2), bool(unbiased), 1.0, need_grad)[0][0]
 
 
 class _SqEuclideanCostFn(torch.autograd.Function):
