@@ -1,5 +1,5 @@
 // The activations of ConvLayer (reference networks/cnn.py:128-147: ReLU, LeakyReLU(0.2), SELU, GELU, SiLU) and their derivatives as
-// device functions: ONE definition for every kernel that applies them unfused (activation.hip, film_act.hip), so that the same
+// device functions: ONE definition for every kernel that applies them unfused (activation.hip, film_act.hip, groupnorm.hip), so that the same
 // input gives the same bits whichever kernel it passes through.  `kind` is an ACT_KINDS value of functional.py.
 #pragma once
 #include <hip/hip_runtime.h>

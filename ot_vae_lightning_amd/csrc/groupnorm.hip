@@ -6,32 +6,7 @@
 // csrc/activation.hip.  Used unfused around the convolution kernels (functional._conv_layer_general), like the non-ReLU activations.
 #include "common.h"
 
-#define SELU_ALPHA 1.6732632423543772848170429916717f
-#define SELU_SCALE 1.0507009873554804934193349852946f
-
-__device__ __forceinline__ float gn_act(float u, int kind) {
-    switch (kind) {
-        case 1: return fmaxf(u, 0.f);
-        case 2: return u > 0.f ? u : 0.2f * u;
-        case 3: return SELU_SCALE * (u > 0.f ? u : SELU_ALPHA * expm1f(u));
-        case 4: return 0.5f * u * (1.f + erff(u * 0.70710678118654752440f));
-        case 5: return u / (1.f + expf(-u));
-        default: return u;
-    }
-}
-__device__ __forceinline__ float gn_act_grad(float u, int kind) {
-    switch (kind) {
-        case 1: return u > 0.f ? 1.f : 0.f;
-        case 2: return u > 0.f ? 1.f : 0.2f;
-        case 3: return u > 0.f ? SELU_SCALE : SELU_SCALE * SELU_ALPHA * expf(u);
-        case 4: return 0.5f * (1.f + erff(u * 0.70710678118654752440f)) + u * 0.39894228040143267794f * expf(-0.5f * u * u);
-        case 5: {
-            const float s = 1.f / (1.f + expf(-u));
-            return s * (1.f + u * (1.f - s));
-        }
-        default: return 1.f;
-    }
-}
+#include "act.h"   // act_fwd / act_grad and the ACT_* kinds, shared with activation.hip and film_act.hip
 
 __device__ __forceinline__ double block_sum256(double v, double* red) {  // all 256 threads; result in every thread
     v = wave_sum(v);
@@ -69,7 +44,7 @@ __global__ __launch_bounds__(256) void group_norm_act_fwd_kernel(const float* __
         const size_t o = (size_t)(e / cg) * C + c;
         float u = (xb[o] - fmu) * frs;
         if (gamma) u = fmaf(u, gamma[g * cg + c], beta[g * cg + c]);
-        ob[o] = gn_act(u, kind);
+        ob[o] = act_fwd(u, kind);
     }
 }
 
@@ -92,7 +67,7 @@ __global__ __launch_bounds__(256) void group_norm_act_bwd_kernel(const float* __
         const float xh = (x[o] - mu) * rs;
         const float gm = gamma ? gamma[g * cg + c] : 1.f;
         const float u = gamma ? fmaf(xh, gm, beta[g * cg + c]) : xh;
-        const float w = ga[o] * gn_act_grad(u, kind) * gm;
+        const float w = ga[o] * act_grad(u, kind) * gm;
         s1 += (double)w;
         s2 += (double)w * (double)xh;
     }
@@ -104,7 +79,7 @@ __global__ __launch_bounds__(256) void group_norm_act_bwd_kernel(const float* __
         const float xh = (x[o] - mu) * rs;
         const float gm = gamma ? gamma[g * cg + c] : 1.f;
         const float u = gamma ? fmaf(xh, gm, beta[g * cg + c]) : xh;
-        const float w = ga[o] * gn_act_grad(u, kind) * gm;
+        const float w = ga[o] * act_grad(u, kind) * gm;
         dx[o] = rs * (w - m1 - xh * m2);
     }
     if (gamma) {  // per-channel parameter partials of this sample: channel c by the threads t == c (mod cg), fixed order over t
@@ -113,7 +88,7 @@ __global__ __launch_bounds__(256) void group_norm_act_bwd_kernel(const float* __
             for (int p = 0; p < HW; ++p) {
                 const size_t o = base + (size_t)p * C + c;
                 const float xh = (x[o] - mu) * rs;
-                const float gu = ga[o] * gn_act_grad(fmaf(xh, gamma[g * cg + c], beta[g * cg + c]), kind);
+                const float gu = ga[o] * act_grad(fmaf(xh, gamma[g * cg + c], beta[g * cg + c]), kind);
                 a += (double)gu * (double)xh;
                 b += (double)gu;
             }

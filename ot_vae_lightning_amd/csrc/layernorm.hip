@@ -2,7 +2,7 @@
 // PositionalEmbedding.LayerNorm :38,54 and the two norms of every nn.TransformerEncoderLayer :169-172; arithmetic of
 // torch.nn.functional.layer_norm: biased variance, eps inside the square root).
 //   y = (x + res - mean) * rstd * gamma + beta        (res: optional residual summed in, the post-norm block's "x + sublayer")
-// One wave per row (D <= 4096): the row lives in registers (D/64 values per lane), mean and centred variance are two
+// One wave per row (D <= 2048): the row lives in registers (D/64 values per lane), mean and centred variance are two
 // wave reductions.  Backward: dx = rstd * (g*gamma - mean(g*gamma) - xhat * mean(g*gamma*xhat)); the parameter gradients are
 // column sums over all rows -- per-block partials in fixed order, then one fixed-order reduction (deterministic).
 #include "common.h"
