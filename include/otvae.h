@@ -122,7 +122,8 @@ int otvae_wgrad_reduce_batched(int n, const float* const* partial, const int* P,
  * layer sizes of this model each one alone fills a fraction of the 256 CUs.  otvae_conv_multi gives exactly the
  * results of otvae_conv_fwd / otvae_conv_bwd_data / otvae_conv_bwd_weight called once per job (same kernels bodies,
  * same fixed-order reductions, same workspace layouts), but packs the MFMA-path jobs into one launch whose workgroups
- * are divided among the jobs; jobs on another path (tiny channel counts) are launched one by one.  No job may read
+ * are divided among the jobs; jobs on another path (image-tile kernels, tiny channel counts) are launched one by one or two by
+ * two (otvae_conv_multi_launches below).  No job may read
  * what another job of the same call writes.  `jobs` is a HOST array. */
 #define OTVAE_JOB_FWD 0
 #define OTVAE_JOB_BWD_DATA 1
@@ -197,6 +198,11 @@ int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream);
  * bit i of packed_mask: job i ran inside one packed conv_jobs_kernel launch; uniform_tap: that launch's template flavour
  * (1 = conv_jobs_kernel<true>), -1 if nothing was packed. */
 int otvae_conv_multi_last(unsigned* packed_mask, int* uniform_tap);
+/* The number of kernel launches the calling thread's last otvae_conv_multi made (immediate weight-gradient reductions included).
+ * Two forward or two data-gradient jobs of the image-tile kernels, or of the direct kernels for tiny channel counts, share ONE launch
+ * when a two-job kernel exists for them (the heads of the ConvBlocks at 8x8 and larger maps); OTVAE_PAIR_LAUNCH=0 in the environment
+ * launches them one by one.  Results are the same bits either way. */
+int otvae_conv_multi_launches(int* n);
 /* Host query, launches nothing: the (tile, tap) visits of the implicit-GEMM launch that serves the forward pass (mode 0) or the data
  * gradient (mode 1) of a layer -- `launch_rule`: every 64-row tile walks each tap some row of the launch can use (the rule before
  * the per-tile list, and of OTVAE_GEMM_LIVE_TAPS=0); `per_tile`: rows position-major, a tile walks the taps one of ITS rows can use.

@@ -81,6 +81,7 @@ SIGNATURES = {
     "otvae_gmm_diag_energy": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "otvae_conv_multi": (i32, [i32, pj, vp]),
     "otvae_conv_multi_last": (i32, [pu32, pi32]),
+    "otvae_conv_multi_launches": (i32, [pi32]),
     "otvae_conv_gemm_chunks": (i32, [pg, i32, pi64, pi64]),
     "otvae_attn_fwd": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "otvae_attn_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),

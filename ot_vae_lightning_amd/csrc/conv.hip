@@ -1747,7 +1747,69 @@ static size_t job_smem_bytes(int kind, int NT) {
     }
 }
 
+// kernel launches of the calling thread's last otvae_conv_multi (the immediate weight-gradient reductions included)
+static thread_local int g_multi_launches = 0;
+
+extern "C" int otvae_conv_multi_launches(int* n) {
+    OTVAE_REQUIRE(n, "otvae_conv_multi_launches: NULL argument");
+    *n = g_multi_launches;
+    return OTVAE_OK;
+}
+
+// A/B switch, read per call as OTVAE_GEMM_LIVE_TAPS is: OTVAE_PAIR_LAUNCH=0 (exactly "0") launches the direct and image-tile jobs of a
+// call one by one, the form before the two-job kernels (the partner of tools/ab_trace.sh and of the bit-equality tests).
+static inline bool pair_launch_on() {
+    const char* e = getenv("OTVAE_PAIR_LAUNCH");
+    return !(e && e[0] == '0' && e[1] == '\0');
+}
+
+enum { PAIR_NONE = 0, PAIR_SMALL = 1, PAIR_TILE = 2 };
+struct PairJob {
+    int idx, cls, kind;  // index in the call; PAIR_SMALL / PAIR_TILE; OTVAE_JOB_FWD / OTVAE_JOB_BWD_DATA
+    DevJob d;
+    TilePlan pl;         // PAIR_TILE
+    dim3 tg;
+    size_t smem;
+};
+
+static TileJobArgs tile_args(const PairJob& p) {
+    const DevJob& d = p.d;
+    TileJobArgs a = {};
+    a.pl = p.pl;
+    a.S = d.a0, a.scale = d.scale, a.shift = d.shift, a.Wg = d.b0, a.bias = d.bias, a.res = d.res;
+    a.xin = d.xin, a.mean = d.mean, a.invstd = d.invstd, a.partial = d.partial, a.fold = d.fold, a.relu = d.relu;
+    if (p.kind == OTVAE_JOB_FWD) a.y = d.out;
+    else a.gv = d.out;
+    a.gx = p.tg.x, a.gy = p.tg.y, a.gz = p.tg.z;
+    return a;
+}
+
+// both jobs (same class, same kind) in one launch, in the order given; -1, nothing launched, when there is no two-job kernel for them
+static int launch_pair_ordered(const PairJob& p, const PairJob& q, hipStream_t st) {
+    if (p.cls == PAIR_TILE)
+        return conv_tile_pair(p.kind == OTVAE_JOB_FWD ? 0 : 1, tile_args(p), tile_args(q), p.smem > q.smem ? p.smem : q.smem, st);
+    if (p.kind == OTVAE_JOB_FWD) {
+        // block counts, as conv_fwd_ex gives the one-job launch
+        const DevJob &a = p.d, &b = q.d;
+        const SmallFwdArgs fa = {a.g, a.a0, a.scale, a.shift, a.b0, a.bias, a.res, a.out, a.partial, a.fold, a.relu, a.cpad, imin(a.gx, 1024)};
+        const SmallFwdArgs fb = {b.g, b.a0, b.scale, b.shift, b.b0, b.bias, b.res, b.out, b.partial, b.fold, b.relu, b.cpad, imin(b.gx, 1024)};
+        return conv_small_fwd_pair(fa, fb, st);
+    }
+    const DevJob &a = p.d, &b = q.d;  // block counts, as conv_bwd_data_ex
+    const SmallDgradArgs da = {a.g, a.a0, a.b0, a.xin, a.scale, a.shift, a.mean, a.invstd, a.out, a.partial, a.relu, a.cpad, a.gx * a.gz};
+    const SmallDgradArgs db = {b.g, b.a0, b.b0, b.xin, b.scale, b.shift, b.mean, b.invstd, b.out, b.partial, b.relu, b.cpad, b.gx * b.gz};
+    return conv_small_dgrad_pair(da, db, st);
+}
+
+// The two-job kernels are instantiated for one order of a pair (the 3x3 branch, then its 1x1 skip); the jobs are independent and every
+// index in them is job-local, so a caller that hands the skip in first gets the same launch with the jobs exchanged.
+static int launch_pair(const PairJob& p, const PairJob& q, hipStream_t st) {
+    const int rc = launch_pair_ordered(p, q, st);
+    return rc == 0 ? 0 : launch_pair_ordered(q, p, st);
+}
+
 static int run_single_job(const otvae_conv_job& jb, void* stream) {
+    g_multi_launches += (jb.kind == OTVAE_JOB_BWD_WEIGHT && !jb.defer_reduce) ? 2 : 1;
     switch (jb.kind) {
         case OTVAE_JOB_FWD: {
             BnFold fold;
@@ -1780,6 +1842,18 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
     hipStream_t st = (hipStream_t)stream;
     g_multi_packed_mask = 0;
     g_multi_packed_ut = -1;
+    g_multi_launches = 0;
+    const bool pair_on = pair_launch_on();
+    // The direct / image-tile job waiting for its sibling (idx < 0: none).  Like the jobs collected in `pack`, it is launched when a job
+    // that cannot join it arrives, or at the end of the call: a call that returns an error for a later job has launched neither.
+    PairJob pend = {};
+    pend.idx = -1;
+    auto flush_pend = [&]() -> int {
+        if (pend.idx < 0) return OTVAE_OK;
+        const int i = pend.idx;
+        pend.idx = -1;
+        return run_single_job(jobs[i], stream);
+    };
     DevJobs pack = {};
     size_t smem = 0;
     int nblocks = 0;
@@ -1804,6 +1878,7 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
             else conv_jobs_rowmajor_kernel<false><<<nblocks, 256, smem, st>>>(pack);
         }
         OTVAE_CHECK_LAUNCH("otvae_conv_multi");
+        ++g_multi_launches;
         for (int i = 0; i < pack.n; ++i) g_multi_packed_mask |= 1u << packed_idx[i];
         g_multi_packed_ut = pack_ut == 1 ? 1 : 0;
         for (int i = 0; i < pack.n; ++i) {  // immediate reductions of the packed weight-gradient jobs
@@ -1814,6 +1889,7 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
             wgrad_reduce_kernel<<<imin(cdiv(total, d.gz >= 32 ? 4 : 64), 2048), 256, 0, st>>>(
                 jb.wpartial, d.gz, d.Kp - (jb.has_bias ? 1 : 0), d.Kp, d.g.Cn, jb.gw, jb.gb);
             OTVAE_CHECK_LAUNCH("otvae_conv_multi(reduce)");
+            ++g_multi_launches;
         }
         pack = {};
         smem = 0;
@@ -1839,6 +1915,10 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
         d.shift = jb.shift;
         bool packable = false;
         const bool ch4 = (g.Cs % 4 == 0) && (g.Cn % 4 == 0);
+        int pcls = PAIR_NONE;  // forward / data-gradient job of the direct or image-tile kernels: may share a launch with its sibling
+        TilePlan tpl = {};
+        dim3 tgrid;
+        size_t tsmem = 0;
         if (jb.kind == OTVAE_JOB_FWD) {
             OTVAE_REQUIRE(jb.x && jb.w && jb.y, "otvae_conv_multi: job %d (forward): NULL tensor", i);
             dim3 grid;
@@ -1851,11 +1931,11 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
             packable = !conv_small_ok(g) && ch4 && aligned16(jb.x) && aligned16(jb.w) &&
                        (jb.scale == nullptr || (aligned16(jb.scale) && aligned16(jb.shift))) &&
                        ((jb.scale == nullptr && jb.fold.slots == nullptr) || g.Cs <= BN_TAB);
-            {
-                TilePlan pl;
-                dim3 tg;
-                size_t sm;
-                if (packable && conv_tile_plan(g, 0, pl, tg, sm)) packable = false;  // image-tile kernel: own launch
+            if (conv_small_ok(g)) {
+                pcls = PAIR_SMALL;
+            } else if (packable && conv_tile_plan(g, 0, tpl, tgrid, tsmem)) {  // image-tile kernel: a launch of its own, or with its sibling
+                packable = false;
+                if (aligned16(jb.y) && (!jb.bias || aligned16(jb.bias)) && (!jb.residual || aligned16(jb.residual))) pcls = PAIR_TILE;
             }
             d.a0 = jb.x;
             d.b0 = jb.w;
@@ -1874,11 +1954,13 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
             dim3 grid;
             dgrad_grid(g, d.NT, grid, d.cpad);
             packable = !conv_small_ok(g) && ch4 && aligned16(jb.gy) && aligned16(jb.w);
-            {
-                TilePlan pl;
-                dim3 tg;
-                size_t sm;
-                if (packable && conv_tile_plan(g, 1, pl, tg, sm)) packable = false;  // image-tile kernel: own launch
+            if (conv_small_ok(g)) {
+                pcls = PAIR_SMALL;
+            } else if (packable && conv_tile_plan(g, 1, tpl, tgrid, tsmem)) {  // image-tile kernel: a launch of its own, or with its sibling
+                packable = false;
+                if (aligned16(jb.gv) && (!jb.x || aligned16(jb.x)) && (!jb.scale || (aligned16(jb.scale) && aligned16(jb.shift))) &&
+                    (!jb.mean || (aligned16(jb.mean) && aligned16(jb.invstd))))
+                    pcls = PAIR_TILE;
             }
             d.a0 = jb.gy;
             d.b0 = jb.w;
@@ -1909,6 +1991,24 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
             d.gx = nkb, d.gy = nnb, d.gz = P;
         }
         if (!packable) {
+            if (pair_on && pcls != PAIR_NONE) {
+                // a job of the direct or image-tile kernels waits for a sibling of its class and kind: both in one launch when a
+                // two-job kernel exists for them, one by one (as with OTVAE_PAIR_LAUNCH=0) otherwise
+                const PairJob cur = {i, pcls, jb.kind, d, tpl, tgrid, tsmem};
+                if (pend.idx >= 0 && pend.cls == cur.cls && pend.kind == cur.kind) {
+                    const int pr = launch_pair(pend, cur, st);
+                    if (pr == 0) {
+                        OTVAE_CHECK_LAUNCH("otvae_conv_multi(pair)");
+                        ++g_multi_launches;
+                        pend.idx = -1;
+                        continue;
+                    }
+                }
+                rc = flush_pend();
+                if (rc) return rc;
+                pend = cur;
+                continue;
+            }
             rc = run_single_job(jb, stream);
             if (rc) return rc;
             continue;
@@ -1927,5 +2027,6 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
         packed_idx[pack.n] = i;
         pack.j[pack.n++] = d;
     }
+    if (int rc = flush_pend()) return rc;
     return flush();
 }

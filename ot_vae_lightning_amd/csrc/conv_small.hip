@@ -86,6 +86,30 @@ __device__ __forceinline__ void store_chan(float* __restrict__ p, const float (&
 // from clamped (always valid) addresses and masked afterwards; the generic tap loop below branches around out-of-image
 // taps, which makes every tap's load wait for the previous tap's arithmetic (9-16 exposed L2 latencies per position:
 // the layers at 32x32 ran at 0.7-1.7 TB/s).
+struct SmallFwdSmem {
+    float w[SMALL_MAXW];  // [tap][c][CNM]  (row padded to CNM when CN is generic)
+    double red[4][2][SMALL_MAXC];
+    float sc[SMALL_MAXC], sh[SMALL_MAXC], b[SMALL_MAXC];
+};
+
+// The body of workgroup `vb` of `nb`: blockIdx.x / gridDim.x in the one-job kernel, the job-local values in the two-job kernel.
+template <int CS, int CN, int KS>
+__device__ __forceinline__ void conv_small_fwd_body(const SmallGeom& g, const float* __restrict__ x,
+                                                    const float* __restrict__ scale, const float* __restrict__ shift,
+                                                    int relu, const float* __restrict__ wT,
+                                                    const float* __restrict__ bias, const float* __restrict__ res,
+                                                    float* __restrict__ y, double* __restrict__ partial, int CnPad,
+                                                    const BnFold& fold, SmallFwdSmem& sm, unsigned vb, unsigned nb) {
+    float* const w_s = sm.w;
+    double(*const redf)[2][SMALL_MAXC] = sm.red;
+    float *const sc_s = sm.sc, *const sh_s = sm.sh, *const b_s = sm.b;
+#define SMALL_VB vb
+#define SMALL_NB nb
+#include "conv_small_fwd_body.h"
+#undef SMALL_VB
+#undef SMALL_NB
+}
+
 template <int CS, int CN, int KS>
 __global__ __launch_bounds__(256) SMALL_OCC void conv_small_fwd_kernel(SmallGeom g, const float* __restrict__ x,
                                                              const float* __restrict__ scale, const float* __restrict__ shift,
@@ -93,125 +117,34 @@ __global__ __launch_bounds__(256) SMALL_OCC void conv_small_fwd_kernel(SmallGeom
                                                              const float* __restrict__ bias, const float* __restrict__ res,
                                                              float* __restrict__ y, double* __restrict__ partial, int CnPad,
                                                              BnFold fold) {
-    constexpr int CSM = CS ? CS : SMALL_MAXC, CNM = CN ? CN : SMALL_MAXC;
-    const int Cs = CS ? CS : g.Cs, Cn = CN ? CN : g.Cn;
     __shared__ __align__(16) float w_s[SMALL_MAXW];  // [tap][c][CNM]  (row padded to CNM when CN is generic)
     __shared__ double redf[4][2][SMALL_MAXC];
     __shared__ float sc_s[SMALL_MAXC], sh_s[SMALL_MAXC], b_s[SMALL_MAXC];
-    const int T = g.KH * g.KW;
-    for (int i = threadIdx.x; i < T * Cs * Cn; i += 256) w_s[i] = wT[i];
-    if (threadIdx.x < SMALL_MAXC) {
-        const int c = threadIdx.x;
-        sc_s[c] = (scale && c < Cs) ? scale[c] : 1.f;
-        sh_s[c] = (scale && c < Cs) ? shift[c] : 0.f;
-        b_s[c] = (bias && c < Cn) ? bias[c] : 0.f;
-    }
-    __syncthreads();
-    if (fold.slots) bn_fold_prologue(fold, Cs, sc_s, sh_s, blockIdx.x == 0);  // the BatchNorm of x folded in (common.h); ends with a barrier
-    const bool affine = scale != nullptr || fold.slots != nullptr;
-    float sc[CSM], sh[CSM];
-#pragma unroll
-    for (int c = 0; c < CSM; ++c) {
-        sc[c] = sc_s[c];
-        sh[c] = sh_s[c];
-    }
-    const int Hu = g.Hs * g.up, Wu = g.Ws * g.up, ush = g.up - 1;
-    const unsigned M = (unsigned)g.N * g.Ho * g.Wo;
-    const float inv_wo = 1.0f / (float)g.Wo, inv_ho = 1.0f / (float)g.Ho;
-    const bool small = M < (1u << 22);
-    double s1[CNM], s2[CNM];
-#pragma unroll
-    for (int j = 0; j < CNM; ++j) s1[j] = s2[j] = 0.0;
-    for (unsigned m = blockIdx.x * 256 + threadIdx.x; m < M; m += gridDim.x * 256) {
-        const unsigned t0 = sdiv(m, g.Wo, inv_wo, small);
-        const int ox = m - t0 * g.Wo;
-        const int n = sdiv(t0, g.Ho, inv_ho, small);
-        const int oy = t0 - (unsigned)n * g.Ho;
-        float acc[CNM];
-#pragma unroll
-        for (int j = 0; j < CNM; ++j) acc[j] = b_s[j];
-        if constexpr (KS > 0 && CS > 0 && CN > 0) {
-            // taps in groups whose loads (<= 32 registers) are in flight together; the clobber keeps a group's loads from
-            // drifting above the previous group's arithmetic (and the weights in LDS, see SMALL_REREAD_LDS)
-            constexpr int GS = (KS * KS * CS <= 32) ? KS * KS : KS;  // all taps at once, or one kernel row at a time
-#pragma unroll
-            for (int t0g = 0; t0g < KS * KS; t0g += GS) {
-                SMALL_REREAD_LDS();
-                float xv[GS][CS];
-                int ok[GS];  // all-ones / zero bit mask: applied with an AND (a select here becomes a branch per channel)
-#pragma unroll
-                for (int i = 0; i < GS; ++i) {
-                    const int t = t0g + i;
-                    const int iy = oy * g.stride + t / KS - g.pad, ix = ox * g.stride + t % KS - g.pad;
-                    ok[i] = ((unsigned)iy < (unsigned)Hu && (unsigned)ix < (unsigned)Wu) ? -1 : 0;
-                    const int cy = min(max(iy, 0), Hu - 1) >> ush, cx = min(max(ix, 0), Wu - 1) >> ush;
-                    load_chan<CS>(x + ((size_t)((unsigned)n * g.Hs + cy) * g.Ws + cx) * CS, xv[i], CS);
-                }
-#pragma unroll
-                for (int i = 0; i < GS; ++i) {
-                    const float* wp = w_s + (t0g + i) * CS * CN;
-#pragma unroll
-                    for (int c = 0; c < CS; ++c) {
-                        const float a = __int_as_float(__float_as_int(act1(xv[i][c], sc[c], sh[c], affine, relu)) & ok[i]);
-#pragma unroll
-                        for (int j = 0; j < CN; ++j) acc[j] = fmaf(a, wp[c * CN + j], acc[j]);
-                    }
-                }
-            }
-        } else {
-            for (int kh = 0; kh < g.KH; ++kh) {
-                const int iy = oy * g.stride + kh - g.pad;
-                if ((unsigned)iy >= (unsigned)Hu) continue;
-                for (int kw = 0; kw < g.KW; ++kw) {
-                    const int ix = ox * g.stride + kw - g.pad;
-                    if ((unsigned)ix >= (unsigned)Wu) continue;
-                    float xv[CSM];
-                    load_chan<CS>(x + ((size_t)((unsigned)n * g.Hs + (iy >> ush)) * g.Ws + (ix >> ush)) * Cs, xv, Cs);
-                    const float* wp = w_s + (kh * g.KW + kw) * Cs * Cn;
-#pragma unroll
-                    for (int c = 0; c < CSM; ++c) {
-                        if (CS || c < Cs) {
-                            const float a = act1(xv[c], sc[c], sh[c], affine, relu);
-#pragma unroll
-                            for (int j = 0; j < CNM; ++j)
-                                if (CN || j < Cn) acc[j] = fmaf(a, wp[c * Cn + j], acc[j]);
-                        }
-                    }
-                }
-            }
-        }
-        if (res) {
-            float rv[CNM];
-            load_chan<CN>(res + (size_t)m * Cn, rv, Cn);
-#pragma unroll
-            for (int j = 0; j < CNM; ++j) acc[j] += rv[j];
-        }
-        store_chan<CN>(y + (size_t)m * Cn, acc, Cn);
-        if (partial) {
-#pragma unroll
-            for (int j = 0; j < CNM; ++j) {
-                s1[j] += (double)acc[j];
-                s2[j] += (double)acc[j] * (double)acc[j];
-            }
-        }
-    }
-    if (partial) {  // per-channel sums of the output = the next layer's BatchNorm statistics
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int j = 0; j < CNM; ++j) {
-            const double a = wave_sum(s1[j]), b = wave_sum(s2[j]);
-            if (lane == 0) {
-                redf[wave][0][j] = a;
-                redf[wave][1][j] = b;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 2 * SMALL_MAXC) {
-            const int which = threadIdx.x / SMALL_MAXC, c = threadIdx.x % SMALL_MAXC;
-            if (c < Cn)
-                bn_stat_out(partial, which, CnPad, c, gridDim.x, blockIdx.x,
-                            (redf[0][which][c] + redf[1][which][c]) + (redf[2][which][c] + redf[3][which][c]));
-        }
+#define SMALL_VB blockIdx.x
+#define SMALL_NB gridDim.x
+#include "conv_small_fwd_body.h"
+#undef SMALL_VB
+#undef SMALL_NB
+}
+
+// Two independent forward jobs (the two branches of a ConvBlock head) in ONE launch: job 0's workgroups, then job 1's; each runs its
+// own job's body -- unchanged -- with its job-local block index and block count.  Two equal bodies are one body called with the
+// selected job's arguments; two different bodies sit in the two arms of a branch.
+template <int CS0, int CN0, int KS0, int CS1, int CN1, int KS1>
+__global__ __launch_bounds__(256) SMALL_OCC void conv_small_fwd_pair_kernel(SmallFwdArgs a, SmallFwdArgs b) {
+    __shared__ __align__(16) SmallFwdSmem sm;
+    if constexpr (CS0 == CS1 && CN0 == CN1 && KS0 == KS1) {
+        // one body serves both jobs: select the job's arguments (a uniform address into the kernel arguments), not the code
+        const bool second = blockIdx.x >= (unsigned)a.nblocks;
+        const SmallFwdArgs& j = second ? b : a;
+        conv_small_fwd_body<CS0, CN0, KS0>(j.g, j.x, j.scale, j.shift, j.relu, j.wT, j.bias, j.res, j.y, j.partial, j.CnPad, j.fold, sm,
+                                           blockIdx.x - (second ? a.nblocks : 0), j.nblocks);
+    } else if (blockIdx.x < (unsigned)a.nblocks) {
+        conv_small_fwd_body<CS0, CN0, KS0>(a.g, a.x, a.scale, a.shift, a.relu, a.wT, a.bias, a.res, a.y, a.partial, a.CnPad, a.fold, sm,
+                                           blockIdx.x, a.nblocks);
+    } else {
+        conv_small_fwd_body<CS1, CN1, KS1>(b.g, b.x, b.scale, b.shift, b.relu, b.wT, b.bias, b.res, b.y, b.partial, b.CnPad, b.fold, sm,
+                                           blockIdx.x - a.nblocks, b.nblocks);
     }
 }
 
@@ -253,6 +186,23 @@ int conv_small_fwd(const SmallGeom& g, int nblocks, const float* x, const float*
 // one lane per SOURCE position (parent pixel when up == 2): all Cs channels, children summed in registers
 // KSU = 0: generic tap loops.  KSU = KS * 16 + STRIDE * 4 + UP (all > 0): square kernel, stride and up-sampling factor
 // known at compile time; the (children x parity-class taps) loads are issued up front from clamped addresses and masked.
+// The statements are in conv_small_dgrad_body.h: once here as a device function of a job-local block index and block count (vb, nb),
+// for the two-job kernel, and once in the one-job kernel below.
+template <int CS, int CN, int KSU>
+__device__ __forceinline__ void conv_small_dgrad_body(const SmallGeom& g, const float* __restrict__ gy,
+                                                      const float* __restrict__ wD, const float* __restrict__ x,
+                                                      const float* __restrict__ scale, const float* __restrict__ shift,
+                                                      int relu, const float* __restrict__ mean,
+                                                      const float* __restrict__ invstd, float* __restrict__ gv,
+                                                      double* __restrict__ partial, int CsPad, float* w_s,
+                                                      double (*red)[2][SMALL_MAXC], unsigned vb, unsigned nb) {
+#define SMALL_VB vb
+#define SMALL_NB nb
+#include "conv_small_dgrad_body.h"
+#undef SMALL_VB
+#undef SMALL_NB
+}
+
 template <int CS, int CN, int KSU>
 __global__ __launch_bounds__(256) SMALL_OCC void conv_small_dgrad_kernel(SmallGeom g, const float* __restrict__ gy,
                                                                const float* __restrict__ wD, const float* __restrict__ x,
@@ -260,139 +210,74 @@ __global__ __launch_bounds__(256) SMALL_OCC void conv_small_dgrad_kernel(SmallGe
                                                                int relu, const float* __restrict__ mean,
                                                                const float* __restrict__ invstd, float* __restrict__ gv,
                                                                double* __restrict__ partial, int CsPad) {
-    constexpr int CSM = CS ? CS : SMALL_MAXC, CNM = CN ? CN : SMALL_MAXC;
-    const int Cs = CS ? CS : g.Cs, Cn = CN ? CN : g.Cn;
     __shared__ __align__(16) float w_s[SMALL_MAXW];  // wD[t][co][c]
     __shared__ double red[4][2][SMALL_MAXC];
-    const int T = g.KH * g.KW;
-    for (int i = threadIdx.x; i < T * Cs * Cn; i += 256) w_s[i] = wD[i];
-    __syncthreads();
-    float sc[CSM], sh[CSM], mu[CSM], is[CSM];
-#pragma unroll
-    for (int c = 0; c < CSM; ++c) {
-        const bool in = CS || c < Cs;
-        sc[c] = (scale && in) ? scale[c] : 1.f;
-        sh[c] = (scale && in) ? shift[c] : 0.f;
-        mu[c] = (mean && in) ? mean[c] : 0.f;
-        is[c] = (mean && in) ? invstd[c] : 0.f;
+#define SMALL_VB blockIdx.x
+#define SMALL_NB gridDim.x
+#include "conv_small_dgrad_body.h"
+#undef SMALL_VB
+#undef SMALL_NB
+}
+
+// The two-job form, as conv_small_fwd_pair_kernel, but with every pointer a kernel parameter of its own: the per-channel scale / shift /
+// mean / invstd reads of the body are scalar loads hoisted out of the position loop only when their pointers are __restrict__ kernel
+// parameters -- through pointers held in a by-value struct they stayed vector loads inside the loop, 182 registers for the 3x3
+// body's 120.
+#define SMALL_DGRAD_PARAMS(s)                                                                                                         \
+    SmallGeom g##s, const float *__restrict__ gy##s, const float *__restrict__ wD##s, const float *__restrict__ x##s,                  \
+        const float *__restrict__ scale##s, const float *__restrict__ shift##s, int relu##s, const float *__restrict__ mean##s,       \
+        const float *__restrict__ invstd##s, float *__restrict__ gv##s, double *__restrict__ partial##s, int CsPad##s, unsigned nb##s
+#define SMALL_DGRAD_ARGS(a) a.g, a.gy, a.wD, a.x, a.scale, a.shift, a.relu, a.mean, a.invstd, a.gv, a.partial, a.CsPad, (unsigned)a.nblocks
+
+template <int CS0, int CN0, int KSU0, int CS1, int CN1, int KSU1>
+__global__ __launch_bounds__(256) SMALL_OCC void conv_small_dgrad_pair_kernel(SMALL_DGRAD_PARAMS(0), SMALL_DGRAD_PARAMS(1)) {
+    __shared__ __align__(16) float w_s[SMALL_MAXW];
+    __shared__ double red[4][2][SMALL_MAXC];
+    if constexpr (CS0 == CS1 && CN0 == CN1 && KSU0 == KSU1) {  // one body: select the job's arguments, not the code
+        const bool j = blockIdx.x >= nb0;
+        conv_small_dgrad_body<CS0, CN0, KSU0>(j ? g1 : g0, j ? gy1 : gy0, j ? wD1 : wD0, j ? x1 : x0, j ? scale1 : scale0,
+                                              j ? shift1 : shift0, j ? relu1 : relu0, j ? mean1 : mean0, j ? invstd1 : invstd0,
+                                              j ? gv1 : gv0, j ? partial1 : partial0, j ? CsPad1 : CsPad0, w_s, red,
+                                              blockIdx.x - (j ? nb0 : 0), j ? nb1 : nb0);
+    } else if (blockIdx.x < nb0)
+        conv_small_dgrad_body<CS0, CN0, KSU0>(g0, gy0, wD0, x0, scale0, shift0, relu0, mean0, invstd0, gv0, partial0, CsPad0, w_s, red,
+                                              blockIdx.x, nb0);
+    else
+        conv_small_dgrad_body<CS1, CN1, KSU1>(g1, gy1, wD1, x1, scale1, shift1, relu1, mean1, invstd1, gv1, partial1, CsPad1, w_s, red,
+                                              blockIdx.x - nb0, nb1);
+}
+
+// The pairs the ConvBlock heads at the image side are made of: two equal 1 -> 8 4x4 stride-2 branches (first encoder block), and the
+// 8 -> 1 up-sampling 3x3 with its 1x1 skip (last decoder block).  (CS, CN, KS) of job 0, of job 1, stride, up.
+#define SMALL_PAIR_CASES(X) X(1, 8, 4, 1, 8, 4, 2, 1) X(8, 1, 3, 8, 1, 1, 1, 2)
+
+static bool small_pair_match(const SmallGeom& a, const SmallGeom& b, int cs0, int cn0, int ks0, int cs1, int cn1, int ks1, int stride,
+                             int up) {
+    return a.Cs == cs0 && a.Cn == cn0 && a.KH == ks0 && a.KW == ks0 && b.Cs == cs1 && b.Cn == cn1 && b.KH == ks1 && b.KW == ks1 &&
+           a.stride == stride && b.stride == stride && a.up == up && b.up == up;
+}
+
+int conv_small_fwd_pair(const SmallFwdArgs& a, const SmallFwdArgs& b, hipStream_t st) {
+#define X(CS0_, CN0_, KS0_, CS1_, CN1_, KS1_, S_, U_)                                                              \
+    if (small_pair_match(a.g, b.g, CS0_, CN0_, KS0_, CS1_, CN1_, KS1_, S_, U_)) {                                  \
+        conv_small_fwd_pair_kernel<CS0_, CN0_, KS0_, CS1_, CN1_, KS1_><<<a.nblocks + b.nblocks, 256, 0, st>>>(a, b); \
+        return 0;                                                                                                  \
     }
-    const unsigned P = (unsigned)g.N * g.Hs * g.Ws;
-    const float inv_ws = 1.0f / (float)g.Ws, inv_hs = 1.0f / (float)g.Hs;
-    const bool small = P < (1u << 22);
-    const int nchild = g.up * g.up;
-    const int smask = g.stride - 1, sshift = g.stride - 1;
-    double s1[CSM], s2[CSM];
-#pragma unroll
-    for (int c = 0; c < CSM; ++c) s1[c] = s2[c] = 0.0;
-    for (unsigned p = blockIdx.x * 256 + threadIdx.x; p < P; p += gridDim.x * 256) {
-        const unsigned t0 = sdiv(p, g.Ws, inv_ws, small);
-        const int sx = p - t0 * g.Ws;
-        const int n = sdiv(t0, g.Hs, inv_hs, small);
-        const int sy = t0 - (unsigned)n * g.Hs;
-        float acc[CSM];
-#pragma unroll
-        for (int c = 0; c < CSM; ++c) acc[c] = 0.f;
-        if constexpr (KSU > 0 && CS > 0 && CN > 0) {
-            constexpr int KS = KSU >> 4, STRIDE = (KSU >> 2) & 3, UP = KSU & 3;
-            constexpr int NT1 = (KS + STRIDE - 1) / STRIDE;  // taps of one parity class per dimension
-            constexpr int NL = UP * UP * NT1 * NT1;
-            constexpr int GS = (NL * CN <= 32) ? NL : NT1 * NT1;  // everything at once, or one child at a time
-#pragma unroll 1  // a real loop over the children: unrolled, the address arithmetic of all NL taps is live at once
-            for (int l0 = 0; l0 < NL; l0 += GS) {
-                SMALL_REREAD_LDS();
-                float gg[GS][CN];
-                int tap[GS];  // kh * KS + kw, or -1 when the tap does not reach an output position
-#pragma unroll
-                for (int i = 0; i < GS; ++i) {
-                    const int l = l0 + i;
-                    const int ch = l / (NT1 * NT1), a = (l / NT1) % NT1, b = l % NT1;
-                    const int iy = sy * UP + ch / UP, ix = sx * UP + ch % UP;
-                    const int kh = ((iy + g.pad) & (STRIDE - 1)) + a * STRIDE, kw = ((ix + g.pad) & (STRIDE - 1)) + b * STRIDE;
-                    const int ty = iy + g.pad - kh, tx = ix + g.pad - kw;
-                    const int oy = ty >> (STRIDE - 1), ox = tx >> (STRIDE - 1);
-                    const bool ok = kh < KS && kw < KS && ty >= 0 && tx >= 0 && oy < g.Ho && ox < g.Wo;
-                    tap[i] = ok ? kh * KS + kw : -1;
-                    const int cy = min(max(oy, 0), g.Ho - 1), cx = min(max(ox, 0), g.Wo - 1);
-                    load_chan<CN>(gy + ((size_t)((unsigned)n * g.Ho + cy) * g.Wo + cx) * CN, gg[i], CN);
-                }
-#pragma unroll
-                for (int i = 0; i < GS; ++i) {
-                    const float* wp = w_s + max(tap[i], 0) * CN * CS;
-#pragma unroll
-                    for (int co = 0; co < CN; ++co) {
-                        const float gval = __int_as_float(__float_as_int(gg[i][co]) & ~(tap[i] >> 31));
-#pragma unroll
-                        for (int c = 0; c < CS; ++c) acc[c] = fmaf(gval, wp[co * CS + c], acc[c]);
-                    }
-                }
-            }
-        } else
-        for (int ch = 0; ch < nchild; ++ch) {
-            const int iy = sy * g.up + (ch >> 1), ix = sx * g.up + (ch & 1);
-            // stride 2: only the taps of this position's parity class contribute; start there and step by the stride
-            for (int kh = (iy + g.pad) & smask; kh < g.KH; kh += g.stride) {
-                const int ty = iy + g.pad - kh;
-                if (ty < 0) break;  // kh only grows
-                const int oy = ty >> sshift;
-                if (oy >= g.Ho) continue;
-                for (int kw = (ix + g.pad) & smask; kw < g.KW; kw += g.stride) {
-                    const int tx = ix + g.pad - kw;
-                    if (tx < 0) break;
-                    const int ox = tx >> sshift;
-                    if (ox >= g.Wo) continue;
-                    float gg[CNM];
-                    load_chan<CN>(gy + ((size_t)((unsigned)n * g.Ho + oy) * g.Wo + ox) * Cn, gg, Cn);
-                    const float* wp = w_s + (kh * g.KW + kw) * Cn * Cs;
-#pragma unroll
-                    for (int co = 0; co < CNM; ++co) {
-                        if (CN || co < Cn) {
-#pragma unroll
-                            for (int c = 0; c < CSM; ++c)
-                                if (CS || c < Cs) acc[c] = fmaf(gg[co], wp[co * Cs + c], acc[c]);
-                        }
-                    }
-                }
-            }
-        }
-        const size_t o = (size_t)p * Cs;
-        float xv[CSM];
-        if (relu || mean) load_chan<CS>(x + o, xv, Cs);
-#pragma unroll
-        for (int c = 0; c < CSM; ++c) {
-            if (CS || c < Cs) {
-                float val = acc[c];
-                if (relu) {
-                    const float v = scale ? fmaf(xv[c], sc[c], sh[c]) : xv[c];
-                    val = v > 0.f ? val : 0.f;
-                }
-                acc[c] = val;
-                if (mean) {
-                    s1[c] += (double)val;
-                    s2[c] += (double)val * (double)((xv[c] - mu[c]) * is[c]);
-                }
-            }
-        }
-        store_chan<CS>(gv + o, acc, Cs);
+    SMALL_PAIR_CASES(X)
+#undef X
+    return -1;
+}
+
+int conv_small_dgrad_pair(const SmallDgradArgs& a, const SmallDgradArgs& b, hipStream_t st) {
+#define X(CS0_, CN0_, KS0_, CS1_, CN1_, KS1_, S_, U_)                                                              \
+    if (small_pair_match(a.g, b.g, CS0_, CN0_, KS0_, CS1_, CN1_, KS1_, S_, U_)) {                                  \
+        conv_small_dgrad_pair_kernel<CS0_, CN0_, KS0_ * 16 + S_ * 4 + U_, CS1_, CN1_, KS1_ * 16 + S_ * 4 + U_>     \
+            <<<a.nblocks + b.nblocks, 256, 0, st>>>(SMALL_DGRAD_ARGS(a), SMALL_DGRAD_ARGS(b));                     \
+        return 0;                                                                                                  \
     }
-    if (mean) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int c = 0; c < CSM; ++c) {
-            const double a = wave_sum(s1[c]), b = wave_sum(s2[c]);
-            if (lane == 0) {
-                red[wave][0][c] = a;
-                red[wave][1][c] = b;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 2 * SMALL_MAXC) {
-            const int which = threadIdx.x / SMALL_MAXC, c = threadIdx.x % SMALL_MAXC;
-            if (c < Cs) {
-                const double t = (red[0][which][c] + red[1][which][c]) + (red[2][which][c] + red[3][which][c]);
-                bn_stat_out(partial, which, CsPad, c, gridDim.x, blockIdx.x, t);
-            }
-        }
-    }
+    SMALL_PAIR_CASES(X)
+#undef X
+    return -1;
 }
 
 int conv_small_dgrad(const SmallGeom& g, int nblocks, const float* gy, const float* wD, const float* x, const float* scale,

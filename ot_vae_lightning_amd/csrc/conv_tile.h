@@ -28,6 +28,25 @@ struct TilePlan {
     TileTaps taps[4];
 };
 
+// one job of a two-job launch (conv_tile_pair): the plan, the arguments of conv_tile_fwd / conv_tile_dgrad, and the job's own grid
+struct TileJobArgs {
+    TilePlan pl;
+    const float* S;       // fwd: x, dgrad: gy
+    const float* scale;
+    const float* shift;
+    const float* Wg;      // fwd: HWIO weight, dgrad: dgrad-layout weight
+    const float* bias;    // fwd
+    const float* res;     // fwd
+    float* y;             // fwd
+    const float* xin;     // dgrad: x
+    const float* mean;    // dgrad
+    const float* invstd;  // dgrad
+    float* gv;            // dgrad
+    double* partial;      // statistics destination (partials or tagged slots), as in the one-job launch
+    BnFold fold;          // fwd
+    int relu, gx, gy, gz;
+};
+
 bool conv_tile_plan(const Geom& g, int mode, TilePlan& pl, dim3& grid, size_t& smem);
 int conv_tile_fwd(const TilePlan& pl, dim3 grid, size_t smem, hipStream_t st, const float* x, const float* scale,
                   const float* shift, int relu, const float* wT, const float* bias, const float* res, float* y,
@@ -35,3 +54,6 @@ int conv_tile_fwd(const TilePlan& pl, dim3 grid, size_t smem, hipStream_t st, co
 int conv_tile_dgrad(const TilePlan& pl, dim3 grid, size_t smem, hipStream_t st, const float* gy, const float* wD,
                     const float* x, const float* scale, const float* shift, int relu, const float* mean,
                     const float* invstd, float* gv, double* partial);
+// Both jobs (same mode: 0 forward, 1 data gradient) in one launch; smem = the larger of the two plans' LDS.  Returns -1, launching
+// nothing, when no kernel is instantiated for the pair (a.pl.nt, a.pl.rbw, b.pl.nt, b.pl.rbw): the caller launches them one by one.
+int conv_tile_pair(int mode, const TileJobArgs& a, const TileJobArgs& b, size_t smem, hipStream_t st);

@@ -2,7 +2,7 @@
 
     python tools/summarize_profiles.py <kernel-stats dir> <tag>         # e.g. gpurun_out/prof8 r01_final
     python tools/summarize_profiles.py --replay <kernel-trace dir> <tag> # replayed (timed) steps only
-    python tools/summarize_profiles.py --launches <kernel-trace dir> <tag> # every implicit-GEMM conv launch of a step, in order
+    python tools/summarize_profiles.py --launches <kernel-trace dir> <tag> [name,name..] # every implicit-GEMM conv launch of a step (or of the named kernels), in order
     python tools/summarize_profiles.py --pmc gpurun_out <tag>           # pmc_fetch / pmc_write / pmc_mfma passes
     python tools/summarize_profiles.py --roofline <tag>                 # joins the replay and PMC summaries
     python tools/summarize_profiles.py --pmc-sq <pmc_sq dir> <tag>      # SQ issue / wait counters per kernel
@@ -239,7 +239,10 @@ if __name__ == "__main__":
     elif sys.argv[1] == "--replay":
         replay_stats(sys.argv[2], sys.argv[3])
     elif sys.argv[1] == "--launches":
-        launch_list(sys.argv[2], sys.argv[3])
+        if len(sys.argv) > 4:   # comma-separated kernel-name fragments instead of the implicit-GEMM default
+            launch_list(sys.argv[2], sys.argv[3], tuple(sys.argv[4].split(",")))
+        else:
+            launch_list(sys.argv[2], sys.argv[3])
     elif sys.argv[1] == "--timeline":
         timeline(sys.argv[2], sys.argv[3])
     else:
