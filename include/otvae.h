@@ -630,6 +630,32 @@ int otvae_moments_accum(int in_dtype, const void* feats, int B, int D, double* n
  * state is {0, 0, +inf, -inf, ...}. */
 int otvae_sqerr_state_words(void);
 int otvae_sqerr_accum(int in_dtype, const void* preds, const void* target, int64_t numel, double* state, void* stream);
+/* StructuralSimilarityIndexMeasure's accumulation (csrc/ssim.hip): preds / target [B][C][H][W] NCHW-contiguous (in_dtype as above) are
+ * each read once.  With E[.] the mean under the separable window wh[kh] x ww[kw] (HOST arrays of weights summing to 1 per axis; they
+ * are rounded to fp32 once and travel in the kernel's argument block) at the (H - kh + 1) (W - kw + 1) positions per plane whose
+ * window lies inside the image:
+ *   mu_p = E[p], mu_t = E[t], s_pp = E[p^2] - mu_p^2, s_tt = E[t^2] - mu_t^2, s_pt = E[p t] - mu_p mu_t,
+ *   ssim = (2 mu_p mu_t + c1) (2 s_pt + c2) / ((mu_p^2 + mu_t^2 + c1) (s_pp + s_tt + c2)),  c1 = (k1 R)^2, c2 = (k2 R)^2,
+ * the second moments formed about one pixel of the workgroup's tile (they are shift-invariant; E[x^2] - mu^2 of the raw values cancels
+ * on narrow-range images), the map evaluated in fp64.  ssim_b is the mean of the map over C and all positions of image b; it depends
+ * on image b alone, bit for bit, whatever B is (range_mode 2 excepted: R is the batch's).  per_image (nullable) [B] receives ssim_b;
+ * state[0] += sum_b ssim_b, state[1] += B.  Fixed reduction order, no atomics, no host read: one launch over the images and a
+ * one-workgroup fold of its partials (range_mode 2: one more launch over the images in front, for R).
+ * range_mode 0: R = range_hi - range_lo, inputs as they are (pass range_lo = 0, range_hi = R); 1: inputs are clamped to
+ * [range_lo, range_hi] at the load, R = range_hi - range_lo; 2: R = max(max p - min p, max t - min t) over this call's tensors, found
+ * on the device by a launch of its own (range_lo / range_hi are ignored).
+ * state: otvae_ssim_state_words() doubles -- {sum ssim_b, image count, two unused words} followed by the range pass's per-workgroup
+ * minima / maxima (contents unspecified between calls).  A fresh state is all zeros.
+ * ws: otvae_ssim_ws(B, C, H, W, kh, kw) bytes -- one double per (image, channel, 16 x 32 tile of positions); the tile and partial
+ * layout depend on C, H, W, kh, kw alone.
+ * OTVAE_EINVAL: null pointers, non-positive sizes, even windows, H < kh or W < kw, range_hi <= range_lo in modes 0 / 1, k1 / k2 < 0.
+ * OTVAE_EUNSUPPORTED (otvae_ssim_ws: -1, as for every refused argument): more than 31 taps on an axis, 2^31 or more tiles or plane
+ * elements. */
+int otvae_ssim_state_words(void);
+int64_t otvae_ssim_ws(int B, int C, int H, int W, int kh, int kw); /* bytes; -1: refused arguments */
+int otvae_ssim_accum(int in_dtype, const void* preds, const void* target, int B, int C, int H, int W, int kh, int kw, const double* wh,
+                     const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi, double* per_image,
+                     double* state, void* ws, void* stream);
 
 /* ---- symmetric eigen-decomposition based matrix functions (ot/matrix_utils.py:37-109) --------------------- */
 /* A[nb][D][D] fp64 symmetric (lower triangle is read, like eigh(UPLO='L')).  fn: 0 = none (eigvals only),

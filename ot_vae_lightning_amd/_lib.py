@@ -170,6 +170,9 @@ SIGNATURES = {
     "otvae_moments_accum": (i32, [i32, vp, i32, i32, vp, vp, vp, vp, vp]),
     "otvae_sqerr_state_words": (i32, []),
     "otvae_sqerr_accum": (i32, [i32, vp, vp, i64, vp, vp]),
+    "otvae_ssim_state_words": (i32, []),
+    "otvae_ssim_ws": (i64, [i32, i32, i32, i32, i32, i32]),
+    "otvae_ssim_accum": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, vp, vp, vp, vp]),
     "otvae_eigh_ws": (i64, [i32, i32]),
     "otvae_eigh_onesided_ws": (i64, [i32, i32]),
     "otvae_eigh_block_onesided_ws": (i64, [i32, i32]),

@@ -20,6 +20,7 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
 
     otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
     otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
+    otvae::ssim_accum               StructuralSimilarityIndexMeasure.update      torchmetrics' ssim      (in place, no gradient)
 
 The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the OT priors,
 ``soft_cross_entropy``, ``gaussian_blur``).
@@ -815,3 +816,47 @@ def _sqerr_accum(preds: Tensor, target: Tensor, state: Tensor) -> None:
 _define("moments_accum", "(Tensor feats, Tensor(a!) n_obs, Tensor(b!) sum_x, Tensor(c!) sum_xx) -> ()", _moments_accum,
         lambda feats, n_obs, sum_x, sum_xx: None)
 _define("sqerr_accum", "(Tensor preds, Tensor target, Tensor(a!) state) -> ()", _sqerr_accum, lambda preds, target, state: None)
+
+SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP, SSIM_RANGE_BATCH = 0, 1, 2   # otvae_ssim_accum's range_mode
+
+
+def _ssim_accum(preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: float, range_mode: int, range_lo: float, range_hi: float,
+                state: Tensor, per_image: Optional[Tensor]) -> None:
+    """``win_h`` / ``win_w``: the window's weights per axis, float64 values of the host (they travel in the kernel's argument block)"""
+    lib = _lib.load()
+    _lib.require_cuda(preds, "preds")
+    _lib.require_cuda(target, "target")
+    if preds.dim() != 4 or preds.shape != target.shape:
+        raise ValueError(f"ssim_accum takes two [B, C, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
+    if preds.dtype not in (torch.float32, torch.float64) or target.dtype != preds.dtype:
+        raise ValueError(f"ssim_accum takes two float32 or two float64 tensors, got {preds.dtype} and {target.dtype}")
+    if not (preds.is_contiguous() and target.is_contiguous()):
+        raise ValueError("ssim_accum: preds and target must be NCHW-contiguous")
+    b, c, h, w = preds.shape
+    kh, kw = len(win_h), len(win_w)
+    if kh % 2 == 0 or kw % 2 == 0 or h < kh or w < kw:
+        raise ValueError(f"ssim_accum: a {kh} x {kw} window must be odd and fit the {h} x {w} images")
+    words = lib.otvae_ssim_state_words()
+    if state.dtype != torch.float64 or state.numel() != words or not state.is_contiguous():
+        raise ValueError(f"ssim_accum: state must be {words} contiguous float64 words")
+    if per_image is not None and (per_image.dtype != torch.float64 or tuple(per_image.shape) != (b,) or not per_image.is_contiguous()):
+        raise ValueError(f"ssim_accum: per_image must be a contiguous float64 tensor of shape ({b},)")
+    if range_mode not in (SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP, SSIM_RANGE_BATCH):
+        raise ValueError(f"ssim_accum: range_mode must be 0, 1 or 2, got {range_mode}")
+    if b == 0 or c == 0:
+        return
+    if kh > 31 or kw > 31:
+        raise NotImplementedError(f"ssim_accum: a {kh} x {kw} window is beyond the kernel's 31 taps per axis")
+    nbytes = lib.otvae_ssim_ws(b, c, h, w, kh, kw)
+    if nbytes < 0:
+        raise NotImplementedError(f"ssim_accum: {tuple(preds.shape)} with a {kh} x {kw} window is beyond the kernel's envelope")
+    ws = torch.empty(nbytes, device=preds.device, dtype=torch.uint8)
+    check(lib.otvae_ssim_accum(0 if preds.dtype == torch.float32 else 1, ptr(preds), ptr(target), b, c, h, w, kh, kw,
+                               (C.c_double * kh)(*win_h), (C.c_double * kw)(*win_w), float(k1), float(k2),
+                               int(range_mode), float(range_lo), float(range_hi), ptr(per_image), ptr(state), ptr(ws), stream()),
+          "otvae_ssim_accum")
+
+
+_define("ssim_accum", "(Tensor preds, Tensor target, float[] win_h, float[] win_w, float k1, float k2, int range_mode, float range_lo, "
+        "float range_hi, Tensor(a!) state, Tensor(b!)? per_image) -> ()", _ssim_accum,
+        lambda preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, state, per_image: None)
