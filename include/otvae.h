@@ -656,6 +656,27 @@ int64_t otvae_ssim_ws(int B, int C, int H, int W, int kh, int kw); /* bytes; -1:
 int otvae_ssim_accum(int in_dtype, const void* preds, const void* target, int B, int C, int H, int W, int kh, int kw, const double* wh,
                      const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi, double* per_image,
                      double* state, void* ws, void* stream);
+/* The gradient of otvae_ssim_accum's per-image values (csrc/ssim_grad.hip; losses.py's SSIMLoss): with an upstream cotangent g[b]
+ * (DEVICE array, fp64) on ssim_b and n = C (H - kh + 1) (W - kw + 1),
+ *   grad_preds[q] = alpha(q) + 2 p_q beta(q) + t_q gamma(q),   alpha, beta, gamma = W^T[(g_b / n) a], W^T[(g_b / n) b], W^T[(g_b / n) c],
+ *   a = 2 mu_t (A2 - A1) / (B1 B2) - 2 mu_p S / B1 + 2 mu_p S / B2,  b = -S / B2,  c = 2 A1 / (B1 B2)
+ * (A1 = 2 mu_p mu_t + c1, A2 = 2 s_pt + c2, B1 = mu_p^2 + mu_t^2 + c1, B2 = s_pp + s_tt + c2, S = A1 A2 / (B1 B2)); W^T is the adjoint
+ * of the valid window filter, separable like it.  The kernel evaluates this about a pixel of the workgroup's tile, as the forward does
+ * (fp32 differences staged, the coefficients in fp64 from the fp32 moments), so alpha and 2 p beta do not cancel on narrow-range
+ * images.  The gradient for target is the same call with preds and target exchanged (S is symmetric).
+ * grad_preds [B][C][H][W] in in_dtype: EVERY element is written, nothing need be zeroed.  One launch, fixed summation order, no atomics,
+ * no host read; image b's gradient depends on image b and g[b] alone, bit for bit.
+ * range_mode 0 and 1 as in otvae_ssim_accum; in mode 1 the gradient is 0 where preds lies strictly outside [range_lo, range_hi]
+ * (torch.clamp's rule: equality passes the gradient).
+ * ws: otvae_ssim_grad_ws(B, C, H, W, kh, kw) bytes -- 0 at present: each workgroup recomputes the moments under its 16 x 32 tile of
+ * pixels in LDS (44 KiB for the 11 x 11 window); ws may then be NULL.
+ * OTVAE_EINVAL: as otvae_ssim_accum, and range_mode 2 (R from the batch depends on the data; a loss needs a fixed scale).
+ * OTVAE_EUNSUPPORTED (otvae_ssim_grad_ws: -1, as for every refused argument): more than 15 taps on an axis (sigma > 2.0 for a Gaussian
+ * window: the tile with its 2 (k - 1) halo no longer fits 64 KiB of LDS), 2^31 or more tiles or plane elements. */
+int64_t otvae_ssim_grad_ws(int B, int C, int H, int W, int kh, int kw); /* bytes; -1: refused arguments */
+int otvae_ssim_grad(int in_dtype, const void* preds, const void* target, int B, int C, int H, int W, int kh, int kw, const double* wh,
+                    const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi, const double* g,
+                    void* grad_preds, void* ws, void* stream);
 
 /* ---- symmetric eigen-decomposition based matrix functions (ot/matrix_utils.py:37-109) --------------------- */
 /* A[nb][D][D] fp64 symmetric (lower triangle is read, like eigh(UPLO='L')).  fn: 0 = none (eigvals only),

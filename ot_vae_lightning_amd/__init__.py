@@ -9,6 +9,8 @@ from .model import *  # noqa: F401,F403
 from .ot import *  # noqa: F401,F403
 from .engine import *  # noqa: F401,F403
 from . import metrics  # noqa: F401
+from . import losses  # noqa: F401
+from .losses import *  # noqa: F401,F403
 from . import transforms  # noqa: F401
 from .transforms import *  # noqa: F401,F403
 from .utils import Collage  # noqa: F401

@@ -173,6 +173,8 @@ SIGNATURES = {
     "otvae_ssim_state_words": (i32, []),
     "otvae_ssim_ws": (i64, [i32, i32, i32, i32, i32, i32]),
     "otvae_ssim_accum": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, vp, vp, vp, vp]),
+    "otvae_ssim_grad_ws": (i64, [i32, i32, i32, i32, i32, i32]),
+    "otvae_ssim_grad": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, vp, vp, vp, vp]),
     "otvae_eigh_ws": (i64, [i32, i32]),
     "otvae_eigh_onesided_ws": (i64, [i32, i32]),
     "otvae_eigh_block_onesided_ws": (i64, [i32, i32]),

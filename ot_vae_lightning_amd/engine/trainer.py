@@ -319,8 +319,9 @@ class HipTrainer:
                 # backward pass (joined with it in flush); only in a captured single-graph step, where that fork exists
                 # ... and only for the package's own `VAE.nelbo`: between `nelbo()` returning and the join in `flush` the loss vector is
                 # not yet written on the launch stream, so a subclass whose nelbo READS the loss it just computed (combining terms,
-                # stacking logs) would capture garbage -- for such a model the value is launched in line
-                own_nelbo = getattr(type(self.model), "nelbo", None) is VAE.nelbo
+                # stacking logs) would capture garbage -- for such a model the value is launched in line; so it is for
+                # `VAE(ssim_loss=...)`, whose nelbo adds the structural term to the vector
+                own_nelbo = getattr(type(self.model), "nelbo", None) is VAE.nelbo and getattr(self.model, "ssim_loss", None) is None
                 on_side = (not cut and STATS_ON_SIDE and own_nelbo and self._segments is None and HF.WGRAD_SIDE_STREAM == 1 and
                            torch.cuda.is_current_stream_capturing())
                 pending._defer[dev] = on_side

@@ -76,7 +76,8 @@ class _Options:
     def window_size(self) -> Tuple[int, int]:
         return len(self.window[0]), len(self.window[1])
 
-    def prepare(self, preds: Tensor, target: Tensor) -> Tuple[Tensor, Tensor]:
+    def prepare(self, preds: Tensor, target: Tensor, detach: bool = True) -> Tuple[Tensor, Tensor]:
+        """shape checks, then both images as contiguous float32 / float64; ``detach=False`` (``losses.SSIMLoss``) keeps them in the graph"""
         if preds.dim() != 4 or target.dim() != 4:
             raise ValueError(f"SSIM takes [B, C, H, W] images, got {tuple(preds.shape)} and {tuple(target.shape)}")
         if preds.shape != target.shape:
@@ -86,7 +87,9 @@ class _Options:
             raise ValueError(f"{preds.shape[2]} x {preds.shape[3]} images are smaller than the {kh} x {kw} window")
         if preds.dtype not in (torch.float32, torch.float64):
             preds = preds.float()
-        return preds.detach().contiguous(), target.detach().to(preds.dtype).contiguous()
+        if detach:
+            preds, target = preds.detach(), target.detach()
+        return preds.contiguous(), target.to(preds.dtype).contiguous()
 
     def accumulate(self, preds: Tensor, target: Tensor, state: Tensor, per_image: Optional[Tensor]) -> None:
         torch.ops.otvae.ssim_accum(preds, target, self.window[0], self.window[1], self.k1, self.k2, self.range_mode, self.range_lo,

@@ -26,7 +26,7 @@ class VAE(VisionModule):
     def __init__(self, *base_args, monitor: str = "psnr", mode: str = "max", prior: Optional[Prior] = None,
                  autoencoder: Optional[nn.Module] = None, encoder: Optional[nn.Module] = None,
                  decoder: Optional[nn.Module] = None, conditional: bool = False, expansion: int = 1,
-                 **base_kwargs) -> None:
+                 ssim_loss: Optional[nn.Module] = None, ssim_weight: float = 1.0, **base_kwargs) -> None:
         super().__init__(*base_args, monitor=monitor, mode=mode, **base_kwargs)
         if autoencoder is None and (encoder is None or decoder is None):
             raise ValueError("At least one of `autoencoder` or (`encoder`, `decoder`) parameters must be set")
@@ -36,6 +36,15 @@ class VAE(VisionModule):
         self.hparams.conditional, self.hparams.expansion = conditional, expansion
         self.loss = self.nelbo
         self.prior = prior
+        # the structural term of the reconstruction loss (losses.SSIMLoss): recon = mse + ssim_weight * ssim_loss(mean reconstruction,
+        # target), added in `nelbo`.  None: `nelbo` issues exactly what it issued before the keyword existed.
+        self.ssim_loss, self.ssim_weight = ssim_loss, float(ssim_weight)
+        if ssim_loss is not None:
+            if getattr(ssim_loss, "reduction", "mean") == "none":
+                raise ValueError("`ssim_loss` must reduce to one value per batch (reduction 'mean' or 'sum'), got reduction='none'")
+            # what the term adds to [total, recon, prior]; resident (nothing is copied from the host inside a captured step) and not
+            # part of the state_dict
+            self.register_buffer("_ssim_mask", torch.tensor([1.0, 1.0, 0.0]), persistent=False)
         if autoencoder is not None:
             assert isinstance(autoencoder, nn.Module) and hasattr(autoencoder, "encode") and hasattr(autoencoder, "decode"), \
                 "Parameter `autoencoder` should be a nn.Module and implement the methods `encode` and `decode`"
@@ -101,6 +110,7 @@ class VAE(VisionModule):
         return self
 
     def recon_loss(self, reconstructions: Tensor, target: Tensor, **kwargs) -> Tensor:
+        """the MSE alone; with ``ssim_loss=`` set, ``nelbo`` adds the structural term to it (and logs the sum as ``train/loss/recon``)"""
         return HF.nelbo_loss(reconstructions, target, None)[1]
 
     def prior_loss(self, prior_loss: Tensor, prior_artifacts, **kwargs) -> Tensor:
@@ -119,6 +129,12 @@ class VAE(VisionModule):
         reconstructions = self.decode(latents, expand_kwargs=True, **kwargs)
         reconstructions_mean = self._reduce_mean(reconstructions)
         out3 = HF.nelbo_loss(reconstructions_mean, target, prior_loss)   # [total, recon, prior/(C*H*W)]
+        if self.ssim_loss is not None:
+            # this READS the vector the kernel just wrote: a training engine launches it in line for such a model (it defers the value
+            # to its side stream only when nothing reads it before the join), and a prior lane that formed it is joined first
+            HF.PriorLane.join(out3.device)
+            s = self.ssim_weight * self.ssim_loss(reconstructions_mean, target)
+            out3 = out3 + s.to(out3.dtype) * self._ssim_mask   # recon and total take the structural term, prior does not
         self._last_out3 = out3.detach()
         self._last_nelbo = out3 if out3.requires_grad else None  # engine.HipTrainer seeds the backward pass here
         loss = out3[0]

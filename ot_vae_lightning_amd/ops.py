@@ -17,6 +17,8 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
                                     gradient, one fused launch
     otvae::soft_cross_entropy       DAD.prior_loss's shifted soft-label CE       model/discrete_auto_diffuser.py:63-72
     otvae::gaussian_blur            torchvision's gaussian_blur (GaussianBlur)   tests/test_latent_transport.py:35
+    otvae::ssim_loss                SSIMLoss: the per-image SSIM values [B] and  torchmetrics' ssim, differentiable
+                                    their gradient for preds and target
 
     otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
     otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
@@ -42,7 +44,7 @@ from ._lib import check, ptr, stream
 __all__ = ["OPS"]
 
 OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior",
-       "soft_cross_entropy", "gaussian_blur", "sliced_w2", "mmd_prior")
+       "soft_cross_entropy", "gaussian_blur", "sliced_w2", "mmd_prior", "ssim_loss")
 _lib_def = torch.library.Library("otvae", "DEF")
 
 
@@ -860,3 +862,88 @@ def _ssim_accum(preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: floa
 _define("ssim_accum", "(Tensor preds, Tensor target, float[] win_h, float[] win_w, float k1, float k2, int range_mode, float range_lo, "
         "float range_hi, Tensor(a!) state, Tensor(b!)? per_image) -> ()", _ssim_accum,
         lambda preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, state, per_image: None)
+
+
+# ------------------------------------------------------------------------------------------------ SSIM as a loss
+def _ssim_loss_check(name: str, preds: Tensor, target: Tensor, win_h, win_w, range_mode: int):
+    """the refusals the forward and the backward share, before any kernel; returns (lib, b, c, h, w, kh, kw)"""
+    lib = _lib.load()
+    _lib.require_cuda(preds, "preds")
+    _lib.require_cuda(target, "target")
+    if preds.dim() != 4 or preds.shape != target.shape:
+        raise ValueError(f"{name} takes two [B, C, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
+    if preds.dtype not in (torch.float32, torch.float64) or target.dtype != preds.dtype:
+        raise ValueError(f"{name} takes two float32 or two float64 tensors, got {preds.dtype} and {target.dtype}")
+    b, c, h, w = preds.shape
+    kh, kw = len(win_h), len(win_w)
+    if kh % 2 == 0 or kw % 2 == 0 or h < kh or w < kw:
+        raise ValueError(f"{name}: a {kh} x {kw} window must be odd and fit the {h} x {w} images")
+    if range_mode not in (SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP):
+        raise ValueError(f"{name}: range_mode must be 0 (fixed) or 1 (clamp), got {range_mode}: a range taken from the batch depends on "
+                         "the data, and a loss needs a fixed scale")
+    if b and c and lib.otvae_ssim_grad_ws(b, c, h, w, kh, kw) < 0:
+        raise NotImplementedError(f"{name}: {tuple(preds.shape)} with a {kh} x {kw} window is beyond the gradient kernel's envelope "
+                                  "(15 taps per axis)")
+    return lib, b, c, h, w, kh, kw
+
+
+def _ssim_loss_fwd(preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: float, range_mode: int, range_lo: float,
+                   range_hi: float) -> Tensor:
+    """``structural_similarity``'s per-image values by the same call of ``otvae_ssim_accum``: the running sums go to a scratch state"""
+    lib, b, c, _, _, _, _ = _ssim_loss_check("ssim_loss", preds, target, win_h, win_w, range_mode)
+    per_image = torch.empty(b, dtype=torch.float64, device=preds.device)
+    if b == 0 or c == 0:
+        return per_image
+    state = torch.empty(lib.otvae_ssim_state_words(), dtype=torch.float64, device=preds.device)   # written, never read
+    _ssim_accum(preds.contiguous(), target.contiguous(), win_h, win_w, k1, k2, range_mode, range_lo, range_hi, state, per_image)
+    return per_image
+
+
+def _ssim_loss_bwd(g: Tensor, preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: float, range_mode: int, range_lo: float,
+                   range_hi: float) -> Tensor:
+    """d sum_b g[b] ssim_b / d preds; for ``target`` the caller exchanges the two images (the map is symmetric)"""
+    lib, b, c, h, w, kh, kw = _ssim_loss_check("ssim_loss_backward", preds, target, win_h, win_w, range_mode)
+    if tuple(g.shape) != (b,):
+        raise ValueError(f"ssim_loss_backward: the cotangent must have shape ({b},), got {tuple(g.shape)}")
+    grad = torch.empty(preds.shape, dtype=preds.dtype, device=preds.device)
+    if b == 0 or c == 0:
+        return grad
+    g = g.to(torch.float64).contiguous()
+    nbytes = lib.otvae_ssim_grad_ws(b, c, h, w, kh, kw)
+    ws = torch.empty(nbytes, device=preds.device, dtype=torch.uint8) if nbytes else None
+    check(lib.otvae_ssim_grad(0 if preds.dtype == torch.float32 else 1, ptr(preds.contiguous()), ptr(target.contiguous()), b, c, h, w, kh,
+                              kw, (C.c_double * kh)(*win_h), (C.c_double * kw)(*win_w), float(k1), float(k2), int(range_mode),
+                              float(range_lo), float(range_hi), ptr(g), ptr(grad), ptr(ws), stream()), "otvae_ssim_grad")
+    return grad
+
+
+_define("ssim_loss", "(Tensor preds, Tensor target, float[] win_h, float[] win_w, float k1, float k2, int range_mode, float range_lo, "
+        "float range_hi) -> Tensor", _ssim_loss_fwd,
+        lambda preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi: preds.new_empty(preds.shape[0], dtype=torch.float64))
+_define("ssim_loss_backward", "(Tensor g, Tensor preds, Tensor target, float[] win_h, float[] win_w, float k1, float k2, int range_mode, "
+        "float range_lo, float range_hi) -> Tensor", _ssim_loss_bwd,
+        lambda g, preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi: preds.new_empty(preds.shape))
+
+
+def _ssim_loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1])
+    ctx.cfg = inputs[2:]
+
+
+def _ssim_loss_backward(ctx, g):
+    preds, target = ctx.saved_tensors
+    need_p, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    gp = torch.ops.otvae.ssim_loss_backward(g, preds, target, *ctx.cfg) if need_p else None
+    gt = torch.ops.otvae.ssim_loss_backward(g, target, preds, *ctx.cfg) if need_t else None
+    return (gp, gt) + (None,) * 7
+
+
+torch.library.register_autograd("otvae::ssim_loss", _ssim_loss_backward, setup_context=_ssim_loss_setup)
+
+
+def _ssim_loss_backward_twice(ctx, g):
+    raise NotImplementedError("otvae::ssim_loss_backward has no derivative of its own: the SSIM loss is differentiable once")
+
+
+# as for the MMD prior: differentiating the backward op is refused aloud instead of returning a silent constant
+torch.library.register_autograd("otvae::ssim_loss_backward", _ssim_loss_backward_twice, setup_context=lambda ctx, inputs, output: None)
