@@ -677,6 +677,28 @@ int64_t otvae_ssim_grad_ws(int B, int C, int H, int W, int kh, int kw); /* bytes
 int otvae_ssim_grad(int in_dtype, const void* preds, const void* target, int B, int C, int H, int W, int kh, int kw, const double* wh,
                     const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi, const double* g,
                     void* grad_preds, void* ws, void* stream);
+/* Kernel Inception Distance (csrc/kid.hip; metrics/kid.py): the unbiased polynomial-kernel MMD^2 of S subsets of m rows each, in one
+ * entry.  real [n_real][D], fake [n_fake][D] fp32 row-major; idx_real / idx_fake [S][m] (device, int32; both NULL: every subset is
+ * rows 0 .. m - 1).  For subset s, x_i = real[idx_real[s][i]], y_j = fake[idx_fake[s][j]], k(a, b) = (gamma <a, b> + coef)^degree:
+ *   per_subset[s] = (sum_{i != j} k(x_i, x_j) + sum_{i != j} k(y_i, y_j)) / (m (m - 1)) - 2 sum_{i, j} k(x_i, y_j) / m^2
+ *   stats = {mean_s per_subset[s], population std (divide by S) of per_subset}
+ * (torchmetrics' poly_kernel / maximum_mean_discrepancy).  gamma is the number to use: the caller resolves "default" to 1 / D.
+ * Features are converted to fp64 while staged, products and the D-long sums run on the fp64 matrix cores, k is evaluated in fp64 by
+ * repeated multiplication; all sums are fp64 in a fixed order (no atomics, no host read), so results are bit-identical from run to
+ * run, and exchanging (real, idx_real) with (fake, idx_fake) gives the same bits.  The rows of a subset are gathered at the load: no
+ * [S][m][D] or [m][m] array exists in memory.  An index outside [0, n) is clamped into it.
+ * ws: otvae_poly_mmd_ws(S, m, D) bytes -- one double per (subset, 128 x 128 tile): S * (nt (nt + 1) + nt^2) * 8 with nt = ceil(m / 128).
+ * OTVAE_EINVAL: null pointers (only one index array included), S < 1, D < 1, m < 2, m > min(n_real, n_fake), degree < 1, NaN gamma / coef.
+ * OTVAE_EUNSUPPORTED (otvae_poly_mmd_ws: -1, as for every refused argument): D > 2048, S > 65535, degree > 8, m > 2^21. */
+int64_t otvae_poly_mmd_ws(int S, int m, int D); /* bytes; -1: refused arguments */
+int otvae_poly_mmd_subsets(const float* real, int64_t n_real, const float* fake, int64_t n_fake, int D, const int32_t* idx_real,
+                           const int32_t* idx_fake, int S, int m, int degree, double gamma, double coef, void* ws, double* per_subset,
+                           double* stats, void* stream);
+/* The feature store of the metric: the B rows of feats [B][D] (in_dtype 0 = fp32, 1 = fp64: ROUNDED to fp32 here) are copied to
+ * buf[count[0] ...] of buf [capacity][D] fp32; rows that would land at or beyond capacity are not stored.  count (device, int64 [2]:
+ * rows stored, rows seen) is read on the device -- a captured call appends at the right place on every replay -- and advanced by a
+ * single-thread launch behind the copy: stored = min(stored + B, capacity), seen += B. */
+int otvae_feature_append(int in_dtype, const void* feats, int B, int D, float* buf, int64_t capacity, int64_t* count, void* stream);
 
 /* ---- symmetric eigen-decomposition based matrix functions (ot/matrix_utils.py:37-109) --------------------- */
 /* A[nb][D][D] fp64 symmetric (lower triangle is read, like eigh(UPLO='L')).  fn: 0 = none (eigvals only),

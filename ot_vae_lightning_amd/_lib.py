@@ -175,6 +175,9 @@ SIGNATURES = {
     "otvae_ssim_accum": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, vp, vp, vp, vp]),
     "otvae_ssim_grad_ws": (i64, [i32, i32, i32, i32, i32, i32]),
     "otvae_ssim_grad": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, vp, vp, vp, vp]),
+    "otvae_poly_mmd_ws": (i64, [i32, i32, i32]),
+    "otvae_poly_mmd_subsets": (i32, [vp, i64, vp, i64, i32, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp]),
+    "otvae_feature_append": (i32, [i32, vp, i32, i32, vp, i64, vp, vp]),
     "otvae_eigh_ws": (i64, [i32, i32]),
     "otvae_eigh_onesided_ws": (i64, [i32, i32]),
     "otvae_eigh_block_onesided_ws": (i64, [i32, i32]),

@@ -1,12 +1,15 @@
 """Validation metrics on the device, with the interface the reference's model code uses and no ``torchmetrics`` dependency:
 ``MetricCollection({"psnr": PeakSignalNoiseRatio(), "fid": FrechetInceptionDistance(net=...)})`` goes into
 ``VAE(metrics=...)`` exactly as in the reference's ``configs/vae/defaults.yaml``.  The accumulation of every ``update`` is one
-HIP entry of ``csrc/metrics.hip`` / ``csrc/ssim.hip`` (``torch.ops.otvae.sqerr_accum`` / ``moments_accum`` / ``ssim_accum``);
-``compute`` runs the fp64 eigensolver."""
+HIP entry of ``csrc/metrics.hip`` / ``csrc/ssim.hip`` / ``csrc/kid.hip`` (``torch.ops.otvae.sqerr_accum`` / ``moments_accum`` /
+``ssim_accum`` / ``feature_append``); the Frechet distance's ``compute`` runs the fp64 eigensolver, the kernel distance's evaluates
+all of its random subsets in one ``torch.ops.otvae.poly_mmd_subsets``."""
 from .base import Metric, MetricCollection
 from .psnr import PeakSignalNoiseRatio
 from .frechet import FrechetDistance, FrechetInceptionDistance, frechet_distance
 from .ssim import StructuralSimilarityIndexMeasure, structural_similarity
+from .kid import KernelDistance, KernelInceptionDistance, kernel_distance, poly_mmd2
 
 __all__ = ["Metric", "MetricCollection", "PeakSignalNoiseRatio", "FrechetDistance", "FrechetInceptionDistance", "frechet_distance",
-           "StructuralSimilarityIndexMeasure", "structural_similarity"]
+           "StructuralSimilarityIndexMeasure", "structural_similarity", "KernelDistance", "KernelInceptionDistance", "kernel_distance",
+           "poly_mmd2"]

@@ -22,6 +22,7 @@ ReduceSpec = Union[str, Sequence[Tuple[int, int, str]]]
 
 class Metric(nn.Module):
     higher_is_better: Optional[bool] = None
+    compute_names: Optional[Tuple[str, ...]] = None   # names of the values of a tuple-valued ``compute`` (``MetricCollection``)
     full_state_update: bool = False
 
     def __init__(self, compute_on_step: bool = False, dist_sync_on_step: bool = False, process_group: Any = None,
@@ -150,12 +151,25 @@ class MetricCollection(nn.ModuleDict):
         for _, metric in self.items(keep_base=True):
             metric.update(*args, **self._filtered(metric, kwargs))
 
+    def _named_results(self, res: Dict[str, Any]) -> Dict[str, Any]:
+        """a metric that declares ``compute_names = ("mean", "std")`` returns a tuple, logged as ``<name>_mean`` and ``<name>_std``"""
+        out = {}
+        for k, v in res.items():
+            names = getattr(self[k], "compute_names", None)
+            if names is None:
+                out[self._name(k)] = v
+            else:
+                if len(names) != len(v):
+                    raise ValueError(f"metric {k!r} declares compute_names {tuple(names)} and returned {len(v)} values")
+                out.update({self._name(f"{k}_{n}"): x for n, x in zip(names, v)})
+        return out
+
     def forward(self, *args, **kwargs) -> Dict[str, Any]:
         res = {k: m(*args, **self._filtered(m, kwargs)) for k, m in self.items(keep_base=True)}
-        return {self._name(k): v for k, v in res.items() if v is not None}
+        return self._named_results({k: v for k, v in res.items() if v is not None})
 
     def compute(self) -> Dict[str, Any]:
-        return {self._name(k): m.compute() for k, m in self.items(keep_base=True)}
+        return self._named_results({k: m.compute() for k, m in self.items(keep_base=True)})
 
     def reset(self) -> None:
         for _, m in self.items(keep_base=True):

@@ -1,7 +1,6 @@
 """Streaming Frechet distance between two feature streams (the reference's ``metrics/fid.py``): per side only
 (n, sum f, sum f f^T) in fp64 is kept, accumulated by ``otvae_moments_accum`` on the fp64 matrix cores; ``compute`` is ``mean_cov``
 and the Gaussian 2-Wasserstein distance through the library's eigensolver."""
-from collections import OrderedDict
 from typing import Optional, Tuple
 
 import torch
@@ -10,6 +9,7 @@ from torch import Tensor
 
 from ..ot import matrix_utils as MU
 from .base import Metric
+from .features import ImageFeatureMixin
 
 __all__ = ["frechet_distance", "FrechetDistance", "FrechetInceptionDistance"]
 
@@ -92,24 +92,7 @@ class FrechetDistance(Metric):
         return frechet_distance(real_mean, real_cov, fake_mean, fake_cov)
 
 
-def _default_inception(feature_size: int) -> nn.Module:
-    valid = [64, 192, 768, 2048]
-    if feature_size not in valid:
-        raise ValueError(f"Integer input to argument `feature` must be one of {valid}, but got {feature_size}.")
-    try:
-        from torchmetrics.image.fid import NoTrainInceptionV3
-    except ImportError as e:
-        raise ImportError("FrechetInceptionDistance(net=None) builds torchmetrics' Inception-v3 feature extractor, and `torchmetrics` "
-                          "(with torch-fidelity) is not importable here: install it, or pass a feature network of your own as `net=`") from e
-
-    class NoTrainInceptionV3NoStateDict(NoTrainInceptionV3):   # the extractor's weights stay out of every checkpoint
-        def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-            return destination if destination is not None else OrderedDict()
-
-    return NoTrainInceptionV3NoStateDict(name="inception-v3-compat", features_list=[str(feature_size)])
-
-
-class FrechetInceptionDistance(FrechetDistance):
+class FrechetInceptionDistance(ImageFeatureMixin, FrechetDistance):
     """The reference's ``FrechetInceptionDistance`` (metrics/fid.py): ``update(generated=None, samples=None)`` takes IMAGES; grey images
     are tiled to three channels, ``to_255`` maps ``data_range`` onto 0 ... 255 and casts to uint8, ``net`` turns them into features that
     are flattened to ``[B, feature_size]`` and accumulated as in ``FrechetDistance``.  ``net=None`` builds torchmetrics' Inception-v3
@@ -118,28 +101,7 @@ class FrechetInceptionDistance(FrechetDistance):
     def __init__(self, net: Optional[nn.Module] = None, feature_size: int = 2048, to_255: bool = False,
                  data_range: Tuple[float, float] = (0., 1.), **metric_kwargs):
         super().__init__(feature_size=feature_size, **metric_kwargs)
-        self.data_range = data_range[1] - data_range[0]
-        self.data_low = data_range[0]
-        if net is None:
-            self.net = _default_inception(feature_size)
-            self.to_255 = tuple(data_range) != (0., 255.)
-        else:
-            self.net = net
-            self.net.eval()
-            self.to_255 = to_255
-
-    def train(self, mode: bool = True):
-        """the feature network never leaves evaluation mode (the model's ``.train()`` reaches the metrics it owns)"""
-        super().train(mode)
-        self.net.eval()
-        return self
-
-    def _extract_features(self, img: Tensor) -> Tensor:
-        if img.size(1) == 1:
-            img = torch.cat([img, img, img], dim=1)
-        if self.to_255:
-            img = (255 * (img - self.data_low) / self.data_range).type(torch.uint8)
-        return self.net(img).reshape(img.shape[0], -1)
+        self._init_features(net, feature_size, to_255, data_range)
 
     @torch.no_grad()
     def update(self, generated: Optional[Tensor] = None, samples: Optional[Tensor] = None) -> None:

@@ -23,6 +23,9 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
     otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
     otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
     otvae::ssim_accum               StructuralSimilarityIndexMeasure.update      torchmetrics' ssim      (in place, no gradient)
+    otvae::feature_append           KernelInceptionDistance.update's store      torchmetrics' kid       (in place, no gradient)
+    otvae::poly_mmd_subsets         KernelInceptionDistance.compute: the MMD^2   torchmetrics' kid       (no gradient)
+                                    of every random subset and their mean / std
 
 The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the OT priors,
 ``soft_cross_entropy``, ``gaussian_blur``).
@@ -818,6 +821,76 @@ def _sqerr_accum(preds: Tensor, target: Tensor, state: Tensor) -> None:
 _define("moments_accum", "(Tensor feats, Tensor(a!) n_obs, Tensor(b!) sum_x, Tensor(c!) sum_xx) -> ()", _moments_accum,
         lambda feats, n_obs, sum_x, sum_xx: None)
 _define("sqerr_accum", "(Tensor preds, Tensor target, Tensor(a!) state) -> ()", _sqerr_accum, lambda preds, target, state: None)
+
+
+# ------------------------------------------------------------------------------------------------ Kernel Inception Distance
+def _poly_mmd_subsets(real: Tensor, fake: Tensor, idx_real: Optional[Tensor], idx_fake: Optional[Tensor], subset_size: int, degree: int,
+                      gamma: float, coef: float):
+    """``gamma`` is the number the kernel uses (the caller resolves the default 1 / D).  Indices must lie in [0, n): they are not read
+    on the host (the kernel clamps a stray one); ``metrics/kid.py`` constructs them in range."""
+    lib = _lib.load()
+    _lib.require_cuda(real, "real features")
+    _lib.require_cuda(fake, "fake features")
+    for name, t in (("real", real), ("fake", fake)):
+        if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"poly_mmd_subsets: {name} must be a contiguous [n, D] float32 tensor, got {tuple(t.shape)} {t.dtype}")
+    if real.shape[1] != fake.shape[1]:
+        raise ValueError(f"poly_mmd_subsets: feature widths differ ({real.shape[1]} and {fake.shape[1]})")
+    if (idx_real is None) != (idx_fake is None):
+        raise ValueError("poly_mmd_subsets: idx_real and idx_fake come together")
+    d, m = real.shape[1], int(subset_size)
+    subsets = 1
+    if idx_real is not None:
+        for name, t in (("idx_real", idx_real), ("idx_fake", idx_fake)):
+            _lib.require_cuda(t, name)
+            if t.dim() != 2 or t.dtype != torch.int32 or not t.is_contiguous() or t.shape[1] != m or t.shape != idx_real.shape:
+                raise ValueError(f"poly_mmd_subsets: {name} must be a contiguous [S, {m}] int32 tensor, got {tuple(t.shape)} {t.dtype}")
+        subsets = idx_real.shape[0]
+    if not 2 <= m <= min(real.shape[0], fake.shape[0]):
+        raise ValueError("Argument `subset_size` should be smaller than the number of samples")
+    if degree < 1 or subsets < 1 or d < 1 or not (gamma == gamma and coef == coef):
+        raise ValueError(f"poly_mmd_subsets: bad argument (subsets {subsets}, width {d}, degree {degree}, gamma {gamma}, coef {coef})")
+    nbytes = lib.otvae_poly_mmd_ws(subsets, m, d)
+    if nbytes < 0 or degree > 8:
+        raise NotImplementedError(f"poly_mmd_subsets: {subsets} subsets of {m} rows, width {d}, degree {degree} is beyond the kernel's "
+                                  "envelope (65535 subsets, width 2048, degree 8)")
+    ws = torch.empty(nbytes, device=real.device, dtype=torch.uint8)
+    per_subset = torch.empty(subsets, device=real.device, dtype=torch.float64)
+    stats = torch.empty(2, device=real.device, dtype=torch.float64)
+    check(lib.otvae_poly_mmd_subsets(ptr(real), real.shape[0], ptr(fake), fake.shape[0], d, ptr(idx_real), ptr(idx_fake), subsets, m,
+                                     int(degree), float(gamma), float(coef), ptr(ws), ptr(per_subset), ptr(stats), stream()),
+          "otvae_poly_mmd_subsets")
+    return per_subset, stats
+
+
+def _poly_mmd_subsets_fake(real, fake, idx_real, idx_fake, subset_size, degree, gamma, coef):
+    subsets = 1 if idx_real is None else idx_real.shape[0]
+    return real.new_empty((subsets,), dtype=torch.float64), real.new_empty((2,), dtype=torch.float64)
+
+
+def _feature_append(feats: Tensor, buf: Tensor, count: Tensor) -> None:
+    lib = _lib.load()
+    _lib.require_cuda(feats, "features")
+    _lib.require_cuda(buf, "feature buffer")
+    _lib.require_cuda(count, "count")
+    if feats.dim() != 2 or feats.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"feature_append takes [B, D] float32 / float64 features, got {tuple(feats.shape)} {feats.dtype}")
+    if buf.dim() != 2 or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.shape[1] != feats.shape[1] or buf.shape[0] < 1:
+        raise ValueError(f"feature_append: the buffer must be a contiguous [capacity, {feats.shape[1]}] float32 tensor, got "
+                         f"{tuple(buf.shape)} {buf.dtype}")
+    if count.dtype != torch.int64 or tuple(count.shape) != (2,) or not count.is_contiguous():
+        raise ValueError(f"feature_append: count must be a contiguous int64 tensor of shape (2,), got {tuple(count.shape)} {count.dtype}")
+    b, d = feats.shape
+    if b == 0 or d == 0:
+        return
+    feats = feats.contiguous()
+    check(lib.otvae_feature_append(0 if feats.dtype == torch.float32 else 1, ptr(feats), b, d, ptr(buf), buf.shape[0], ptr(count),
+                                   stream()), "otvae_feature_append")
+
+
+_define("poly_mmd_subsets", "(Tensor real, Tensor fake, Tensor? idx_real, Tensor? idx_fake, int subset_size, int degree, float gamma, "
+        "float coef) -> (Tensor per_subset, Tensor stats)", _poly_mmd_subsets, _poly_mmd_subsets_fake)
+_define("feature_append", "(Tensor feats, Tensor(a!) buf, Tensor(b!) count) -> ()", _feature_append, lambda feats, buf, count: None)
 
 SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP, SSIM_RANGE_BATCH = 0, 1, 2   # otvae_ssim_accum's range_mode
 
