@@ -619,6 +619,13 @@ class PriorLane:
         return PriorLane._Section(device)
 
     @staticmethod
+    def issue(device, fn, *held):
+        """``fn()`` issued on the lane, its launch-stream operands ``held`` until the join; returns what ``fn`` returns"""
+        PriorLane.hold(device, *held)
+        with PriorLane.section(device):
+            return fn()
+
+    @staticmethod
     def join(device) -> None:
         """the launch stream waits for the lane's work (no-op when nothing is outstanding)"""
         done = PriorLane._open.get(device)

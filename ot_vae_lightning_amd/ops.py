@@ -61,6 +61,19 @@ def _define(name: str, schema: str, impl, fake, tags=()):
     torch.library.register_fake(f"otvae::{name}")(fake)
 
 
+def _refuse_second_derivative(op_name: str, what: str):
+    """an Autograd kernel for a backward op too: differentiating it twice is refused aloud instead of returning a silent constant"""
+    def refuse(ctx, *grads):
+        raise NotImplementedError(f"otvae::{op_name} has no derivative of its own: the {what} is differentiable once")
+
+    torch.library.register_autograd(f"otvae::{op_name}", refuse, setup_context=lambda ctx, inputs, output: None)
+
+
+def _dense_or_none(gadd: Optional[Tensor]) -> Optional[Tensor]:
+    """the optional ``gadd`` operand of the prior backward ops (the gradient reaching z through its other consumer), densely laid out"""
+    return gadd.contiguous() if gadd is not None else None
+
+
 # ------------------------------------------------------------------------------------------------ attention
 def _attn_fwd(qkv: Tensor, heads: int, scale: float, need_aux: bool):
     from .functional import as_nhwc
@@ -272,10 +285,9 @@ def _nelbo_fwd(pred: Tensor, target: Tensor, prior_loss: Optional[Tensor], chw: 
     from .functional import PriorLane
     if PriorLane.is_open(pred.device) and PriorLane.active(pred.device):
         # the prior term is still being computed on the prior lane (functional.PriorLane): the loss vector is formed there too,
-        # behind it -- the backward pass needs pred and target, not this value
-        PriorLane.hold(pred.device, pred, target, prior_loss)
-        with PriorLane.section(pred.device):
-            return _nelbo_fwd_launch(pred, target, prior_loss, chw, allow_defer=False)  # (ordered behind the lane's work, not the side stream's)
+        # behind it -- the backward pass needs pred and target, not this value (ordered behind the lane's work, not the side stream's)
+        return PriorLane.issue(pred.device, lambda: _nelbo_fwd_launch(pred, target, prior_loss, chw, allow_defer=False),
+                               pred, target, prior_loss)
     return _nelbo_fwd_launch(pred, target, prior_loss, chw)
 
 
@@ -361,7 +373,7 @@ def _sk_bwd(g: Tensor, gadd: Optional[Tensor], z: Tensor, y: Tensor, pi: Tensor,
     z, y = z.contiguous(), y.to(z.dtype).contiguous()
     n, d = z.shape
     gz = torch.empty_like(z)
-    gadd = gadd.contiguous() if gadd is not None else None
+    gadd = _dense_or_none(gadd)
     check(_lib.load().otvae_ot_cost_grad(0 if z.dtype == torch.float32 else 1, ptr(z), ptr(y), ptr(pi), ptr(g.contiguous()), g.numel(),
                                          float(scale), ptr(gadd), n, y.shape[0], d, ptr(gz), stream()), "otvae_ot_cost_grad")
     return gz
@@ -422,7 +434,7 @@ def _sw_bwd(g: Tensor, gadd: Optional[Tensor], resid: Tensor, theta: Tensor, sca
     nl, n = resid.shape
     d = theta.shape[1]
     gz = torch.empty((n, d), device=resid.device, dtype=torch.float32)
-    gadd = gadd.contiguous() if gadd is not None else None
+    gadd = _dense_or_none(gadd)
     check(_lib.load().otvae_sliced_w2_bwd(ptr(g.float().contiguous()), ptr(gadd), ptr(resid.contiguous()), ptr(theta.contiguous()), n, d, nl,
                                           float(scale), ptr(gz), stream()), "otvae_sliced_w2_bwd")
     return gz
@@ -448,14 +460,7 @@ def _sw_backward(ctx, g, _gresid, _gtheta):
 
 
 torch.library.register_autograd("otvae::sliced_w2", _sw_backward, setup_context=_sw_setup)
-
-
-def _sw_backward_twice(ctx, g):
-    raise NotImplementedError("otvae::sliced_w2_backward has no derivative of its own: the sliced W2 prior is differentiable once")
-
-
-# an Autograd kernel for the backward op too: differentiating it twice is refused aloud instead of returning a silent constant
-torch.library.register_autograd("otvae::sliced_w2_backward", _sw_backward_twice, setup_context=lambda ctx, inputs, output: None)
+_refuse_second_derivative("sliced_w2_backward", "sliced W2 prior")
 
 
 # ------------------------------------------------------------------------------------------------ MMD prior
@@ -528,7 +533,7 @@ def _mmd_bwd(g: Tensor, gadd: Optional[Tensor], G: Tensor):
         raise ValueError("mmd_prior_backward: the forward ran with need_grad=False and kept no gradient")
     gz = torch.empty((n, d), device=G.device, dtype=torch.float32)
     g = g.float().contiguous()
-    gadd = gadd.contiguous() if gadd is not None else None
+    gadd = _dense_or_none(gadd)
     check(_lib.load().otvae_mmd_bwd(ptr(g), g.numel(), ptr(gadd), ptr(G.contiguous()), n, d, ptr(gz), stream()), "otvae_mmd_bwd")
     return gz
 
@@ -557,14 +562,7 @@ def _mmd_backward(ctx, g, _gG, _gterms):
 
 
 torch.library.register_autograd("otvae::mmd_prior", _mmd_backward, setup_context=_mmd_setup)
-
-
-def _mmd_backward_twice(ctx, g):
-    raise NotImplementedError("otvae::mmd_prior_backward has no derivative of its own: the MMD prior is differentiable once")
-
-
-# as for the sliced prior: differentiating the backward op is refused aloud instead of returning a silent constant
-torch.library.register_autograd("otvae::mmd_prior_backward", _mmd_backward_twice, setup_context=lambda ctx, inputs, output: None)
+_refuse_second_derivative("mmd_prior_backward", "MMD prior")
 
 
 # ------------------------------------------------------------------------------------------------ Gaussian W2 prior
@@ -611,7 +609,7 @@ def _w2_bwd(g: Tensor, gadd: Optional[Tensor], z: Tensor, mu: Tensor, q: Tensor,
     if rt is not None:
         w = MU.matmul64(MU.matmul64(rt, w), rt)                  # covt^1/2 M^-1/2 covt^1/2
     gz = torch.empty_like(z)
-    gadd = gadd.contiguous() if gadd is not None else None
+    gadd = _dense_or_none(gadd)
     check(lib.otvae_w2_prior_bwd(0 if z.dtype == torch.float32 else 1, ptr(z), b, d, ptr(mu), ptr(mut), ptr(w),
                                  ptr(g.float().contiguous()), g.numel(), float(scale), ptr(gadd), ptr(gz), stream()),
           "otvae_w2_prior_bwd")
@@ -1012,11 +1010,4 @@ def _ssim_loss_backward(ctx, g):
 
 
 torch.library.register_autograd("otvae::ssim_loss", _ssim_loss_backward, setup_context=_ssim_loss_setup)
-
-
-def _ssim_loss_backward_twice(ctx, g):
-    raise NotImplementedError("otvae::ssim_loss_backward has no derivative of its own: the SSIM loss is differentiable once")
-
-
-# as for the MMD prior: differentiating the backward op is refused aloud instead of returning a silent constant
-torch.library.register_autograd("otvae::ssim_loss_backward", _ssim_loss_backward_twice, setup_context=lambda ctx, inputs, output: None)
+_refuse_second_derivative("ssim_loss_backward", "SSIM loss")

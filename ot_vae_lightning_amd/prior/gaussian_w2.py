@@ -15,48 +15,12 @@ import torch
 from torch import Tensor
 
 from .. import ops as _ops  # noqa: F401  (registers torch.ops.otvae.*)
-from .base import Prior
+from .base import MinibatchPrior, Prior, _LatentLossFn
 
 __all__ = ["GaussianW2Prior"]
 
 
-class _W2PriorFn(torch.autograd.Function):
-    """``torch.ops.otvae.gaussian_w2_prior`` / ``..._backward`` (ops.py) plus one thing an operator cannot do: the latents leave
-    through this node too (an alias of z, see prior/sinkhorn.py), so the decoder's gradient is added inside the backward kernel."""
-
-    @staticmethod
-    def forward(ctx, z, mut, covt, rt, v_init, warm, scale):
-        from ..functional import PriorLane
-        ctx.lane = PriorLane.active(z.device)
-        if ctx.lane:  # beside the decoder, on the prior lane of a training engine's step (functional.PriorLane)
-            PriorLane.hold(z.device, z, mut, covt, rt)
-            with PriorLane.section(z.device):
-                loss, mu, q, vt = torch.ops.otvae.gaussian_w2_prior(z, mut, covt, rt, v_init, warm, float(scale))
-                if v_init is not None:  # the warm-start basis of the next step, behind the solve that produced it
-                    v_init.copy_(vt)
-                    warm.fill_(1)
-        else:
-            loss, mu, q, vt = torch.ops.otvae.gaussian_w2_prior(z, mut, covt, rt, v_init, warm, float(scale))
-        ctx.save_for_backward(z, mu, q)
-        ctx.target = (mut, rt)
-        ctx.scale = float(scale)
-        ctx.mark_non_differentiable(vt)
-        return z.view_as(z), loss, vt
-
-    @staticmethod
-    def backward(ctx, gz_out, g, _gvt):
-        z, mu, q = ctx.saved_tensors
-        mut, rt = ctx.target
-        if ctx.lane:
-            from ..functional import PriorLane
-            PriorLane.join(z.device)
-        if g is None:
-            return gz_out, None, None, None, None, None, None
-        return (torch.ops.otvae.gaussian_w2_prior_backward(g, gz_out, z, mu, q, mut, rt, ctx.scale), None, None, None, None, None,
-                None)
-
-
-class GaussianW2Prior(Prior):
+class GaussianW2Prior(MinibatchPrior):
     """Deterministic encoder + W2^2( N(mean_B, cov_B), N(target_mean, target_cov) ) of the minibatch of latents (flattened to
     [B, D]); ``target_mean`` / ``target_cov`` default to the standard normal.  ``forward`` returns (z, loss[B], artifacts) with
     every loss entry equal to the distance, so the VAE's ``prior_loss.mean()`` is the distance.  The batch must hold more
@@ -81,9 +45,6 @@ class GaussianW2Prior(Prior):
         # (1e-12 after 1e8 of them), far below what the loss resolves.
         self.register_buffer("_warm", torch.zeros(1, dtype=torch.int32), persistent=False)
         self._v_prev = None
-
-    def out_size(self, size):
-        return size
 
     def _otvae_step_state(self, latent_shape, device):
         """(engine.HipTrainer's step guard) the warm-start basis is state a training step rewrites without being a registered buffer:
@@ -117,10 +78,6 @@ class GaussianW2Prior(Prior):
             self._root = (cov.contiguous(), root.contiguous())
         return self._root
 
-    def forward(self, x: Tensor, step: int) -> Prior.EncodingResults:
-        # loss_coeff x annealing is folded into the tail kernel (and the backward's scale): no separate multiply
-        return self.encode(x, _scale=float(self.loss_coeff * self.annealing(step)))
-
     def encode(self, x: Tensor, _scale: float = 1.0) -> Prior.EncodingResults:
         zf = x.flatten(1)
         if self.target_cov is not None and self.target_cov.shape[-1] != zf.shape[1]:
@@ -131,11 +88,17 @@ class GaussianW2Prior(Prior):
         if warm_ok and (self._v_prev is None or self._v_prev.shape[-1] != d or self._v_prev.device != zf.device):
             self._v_prev = torch.zeros((1, d, d), device=zf.device, dtype=torch.float64)
             self._warm.zero_()
-        z_out, loss, vt = _W2PriorFn.apply(zf, self.target_mean, covt, rt, self._v_prev if warm_ok else None,
-                                           self._warm if warm_ok else None, _scale)
-        from ..functional import PriorLane
-        if warm_ok and not PriorLane.active(zf.device):  # (on the prior lane the node itself refreshed the basis, behind its solve)
-            with torch.no_grad():
-                self._v_prev.copy_(vt)
-                self._warm.fill_(1)
+        mut, scale = self.target_mean, float(_scale)
+        v_init, warm = (self._v_prev, self._warm) if warm_ok else (None, None)
+
+        def run():
+            loss, mu, q, vt = torch.ops.otvae.gaussian_w2_prior(zf, mut, covt, rt, v_init, warm, scale)
+            if v_init is not None:  # the warm-start basis of the next step, behind the solve that produced it
+                v_init.copy_(vt)
+                warm.fill_(1)
+            return loss, (zf, mu, q), ()
+
+        z_out, loss = _LatentLossFn.apply(
+            zf, run, lambda g, gadd, z, mu, q: torch.ops.otvae.gaussian_w2_prior_backward(g, gadd, z, mu, q, mut, rt, scale),
+            mut, covt, rt)
         return z_out.view(x.shape), loss, {}

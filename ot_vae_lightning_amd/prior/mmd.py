@@ -6,53 +6,24 @@
     MMD2 = 1/(N(N-1)) sum_{i != j} k(r(z_i, z_j)) + 1/(M(M-1)) sum_{i != j} k(r(y_i, y_j)) - 2/(N M) sum_{i, j} k(r(z_i, y_j))
     (unbiased=False: 1/N^2, 1/M^2 and the diagonal k(0) in the sums)
 
-No iteration, no sort, any N against any M, nothing of size N x M in memory."""
+No iteration, no sort, any N against any M, nothing of size N x M in memory.
+
+Forward = ``torch.ops.otvae.mmd_prior`` -> ``otvae_mmd_fwd`` (Gram tile, kernel function and gradient product in one launch, fixed-order
+finish), backward = ``otvae_mmd_bwd`` (one element-wise launch that also adds the decoder's gradient): no library GEMM and no ATen
+kernel on either side."""
 from typing import Optional, Sequence
 
 import torch
 from torch import Tensor
 
-from .base import Prior
+from .base import MinibatchPrior, Prior, _LatentLossFn
 
 __all__ = ["MMDPrior"]
 
 DEFAULT_SCALES = (0.1, 0.2, 0.5, 1.0, 2.0, 5.0, 10.0)
 
 
-class _MMDLossFn(torch.autograd.Function):
-    """Forward = ``torch.ops.otvae.mmd_prior`` -> ``otvae_mmd_fwd`` (Gram tile, kernel function and gradient product in one launch,
-    fixed-order finish), backward = ``otvae_mmd_bwd`` (one element-wise launch that also adds the decoder's gradient): no library
-    GEMM and no ATen kernel on either side."""
-
-    @staticmethod
-    def forward(ctx, z, y, cfg, scale, need_grad):
-        from ..functional import PriorLane
-        ctx.lane = PriorLane.active(z.device)
-        if ctx.lane:  # beside the decoder, on the prior lane of a training engine's step (functional.PriorLane)
-            PriorLane.hold(z.device, z, y)
-            with PriorLane.section(z.device):
-                loss, G, terms = torch.ops.otvae.mmd_prior(z, y, *cfg, float(scale), need_grad)
-        else:
-            loss, G, terms = torch.ops.otvae.mmd_prior(z, y, *cfg, float(scale), need_grad)
-        ctx.save_for_backward(G)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(terms)
-        # the latents leave through this node too (an alias of z, see prior/sinkhorn.py): the gradient the decoder sends back is added
-        # inside otvae_mmd_bwd instead of by an autograd accumulation kernel
-        return z.view_as(z), loss, terms
-
-    @staticmethod
-    def backward(ctx, gz_out, g, _gterms):
-        (G,) = ctx.saved_tensors
-        if ctx.lane:
-            from ..functional import PriorLane
-            PriorLane.join(G.device)  # the gradient (and the loss vector behind it) is complete from here on
-        if g is None:  # only the latents were used downstream
-            return gz_out, None, None, None, None
-        return torch.ops.otvae.mmd_prior_backward(g, gz_out, G), None, None, None, None
-
-
-class MMDPrior(Prior):
+class MMDPrior(MinibatchPrior):
     """Deterministic encoder + MMD2 between the minibatch of latents and M draws of N(0, sigma2 I).  ``forward`` returns
     (z, loss[B], artifacts) with loss[b] = loss_coeff x annealing x MMD2 (identical for every b, so that the VAE's ``prior_loss.mean()``
     equals it; MMD2 of the unbiased estimator may be negative); artifacts = {"prior_samples", "mmd_terms"}: the draws y [M, D] and
@@ -73,22 +44,11 @@ class MMDPrior(Prior):
         self.unbiased = bool(unbiased)
         self.seed = seed
 
-    def out_size(self, size):
-        return size
-
     def sample(self, shape, device) -> Tensor:
         return torch.randn(*shape, device=device) * self.sigma2 ** 0.5
 
-    def _key(self, device) -> Tensor:
-        from .. import functional as HF
-        key = self.__dict__.get("_rng_key")
-        if key is None or key.device != device:
-            key = self.__dict__["_rng_key"] = HF.new_rng_key(device, self.seed)
-        return key
-
     def forward(self, x: Tensor, step: int, prior_samples: Optional[Tensor] = None) -> Prior.EncodingResults:
-        # loss_coeff x annealing is folded into the loss kernel (and the gradient it leaves): no separate multiply
-        return self.encode(x, prior_samples=prior_samples, _scale=float(self.loss_coeff * self.annealing(step)))
+        return super().forward(x, step, prior_samples=prior_samples)
 
     def encode(self, x: Tensor, prior_samples: Optional[Tensor] = None, _scale: float = 1.0) -> Prior.EncodingResults:
         from .. import _lib, ops
@@ -113,5 +73,10 @@ class MMDPrior(Prior):
                 ys = prior_samples
         cfg = (ops.MMD_KERNELS[self.kernel], list(self.scales), self.sigma2, self.unbiased)
         need_grad = bool(torch.is_grad_enabled() and zf.requires_grad)   # validation / no_grad: the gradient product is skipped
-        z_out, loss, terms = _MMDLossFn.apply(zf, ys, cfg, _scale, need_grad)
+
+        def run():
+            loss, G, terms = torch.ops.otvae.mmd_prior(zf, ys, *cfg, float(_scale), need_grad)
+            return loss, (G,), (terms,)
+
+        z_out, loss, terms = _LatentLossFn.apply(zf, run, torch.ops.otvae.mmd_prior_backward, ys)
         return z_out.view(z.shape), loss, {"prior_samples": prior_samples, "mmd_terms": terms}

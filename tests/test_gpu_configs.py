@@ -1000,7 +1000,7 @@ def test_side_stream_weight_gradients_equal_single_stream(A, monkeypatch):
     assert not HF._PendingReduce._state[dev] and not HF._PendingReduce._held.get(dev) and not HF._PendingReduce._wq[dev][0]
 
 
-@pytest.mark.parametrize("prior_kind", ["sinkhorn", "gaussian_w2"])
+@pytest.mark.parametrize("prior_kind", ["sinkhorn", "gaussian_w2", "sliced", "mmd"])
 def test_prior_lane_equals_in_line_order(A, prior_kind, monkeypatch):
     """inside a captured step the prior's optimal-transport work (Sinkhorn solve / statistics + eigh + W2 tail) and
     the loss vector run on a stream of their own beside the decoder (functional.PriorLane).  Same kernels, same inputs: losses,
@@ -1014,7 +1014,9 @@ def test_prior_lane_equals_in_line_order(A, prior_kind, monkeypatch):
         torch.manual_seed(11)
         enc = A.CNN(1, 128, 32, 1, capacity=8, down_sample=True, residual="add")
         dec = A.CNN(128, 1, 1, 32, capacity=8, up_sample=True, residual="add")
-        prior = A.SinkhornPrior(reg=0.05, max_iter=50, threshold=0.0, seed=7) if prior_kind == "sinkhorn" else A.GaussianW2Prior(loss_coeff=0.1)
+        prior = {"sinkhorn": lambda: A.SinkhornPrior(reg=0.05, max_iter=50, threshold=0.0, seed=7),
+                 "gaussian_w2": lambda: A.GaussianW2Prior(loss_coeff=0.1),
+                 "sliced": lambda: A.SlicedWassersteinPrior(seed=7), "mmd": lambda: A.MMDPrior(seed=7)}[prior_kind]()
         model = A.VAE(encoder=enc, decoder=dec, prior=prior).cuda().train()
         tr = A.HipTrainer(model, batch_shape=(B, 1, 32, 32), use_graph=True)
         outs = [tr.step(x).clone() for x in xs]
