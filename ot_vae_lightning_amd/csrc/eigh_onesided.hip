@@ -21,13 +21,13 @@
 //     iteration: within such a +-lambda pair the columns of G are orthogonal for ANY rotation of the two eigenvectors, so the
 //     iteration may stop at mixtures v with |v . A v| < |A v|.  hj_finish_kernel tests every pair for |v_k . g_k| = |g_k| and,
 //     when one fails, the three kernels run a second time on A + |A|_inf I (pass 1; they return at once otherwise).
-//   * round 3: a positive definite A (the covariances this solver exists for) is first FACTORED in place in LDS, A = U^T U (upper
+//   * a positive definite A (the covariances this solver exists for) is first FACTORED in place in LDS, A = U^T U (upper
 //     Cholesky, right-looking, ~80 us at D = 128), and the iteration runs on the columns of L = U^T -- position j starts as row j of
 //     U.  One-sided Jacobi on L computes L V = Q S, so A = L L^T = Q S^2 Q^T: eigenvalues are the squared column norms and the
 //     eigenvectors are the NORMALISED FINAL COLUMNS themselves -- no rotation replay on V at all -- and the iteration sees
 //     cond(A)^1/2 instead of cond(A)^2: 9 sweeps instead of 16 on covariance-like 128 x 128 matrices (numpy restatement of this
 //     ordering; columns of L^T would need 11).  A non-positive pivot (semi-definite or indefinite input) puts A back and takes the
-//     path above.  OTVAE_EIGH_NO_CHOL=1 switches the factorisation off (A/B).
+//     path above, as does a warm start (the caller's basis, not the factor, supplies the starting columns).
 // Arithmetic is fp64 throughout; the iteration ends after the first sweep without a rotation.  A matrix that is still rotating
 // after HJ_MAX_SWEEPS sweeps gets NaN eigenvalues (loud, like a starved Sinkhorn solve) instead of an unconverged answer.
 #include <type_traits>
@@ -137,8 +137,7 @@ __device__ __forceinline__ double nr_rsq(double x) {
 // one workgroup of 512 threads per matrix: L lanes per pair slot (8 for D > 64: 64 slots; 16 below), rows strided by L
 template <int L>
 __global__ __launch_bounds__(512) void hj_sweep_kernel(const double* __restrict__ Ain, int D, void* __restrict__ ws,
-                                                        const double* __restrict__ G0in, const int* __restrict__ warm, int pass,
-                                                        int use_chol) {
+                                                        const double* __restrict__ G0in, const int* __restrict__ warm, int pass) {
     if (pass == 1 && hj_ws(ws, blockIdx.x, D).ctl->redo == 0) return;  // uniform over the workgroup
     // the start basis counts only once the caller's flag says it holds one; the second pass starts cold on the shifted matrix
     const double* __restrict__ G0 = (pass == 0 && G0in && (!warm || warm[0])) ? G0in : nullptr;
@@ -200,7 +199,12 @@ __global__ __launch_bounds__(512) void hj_sweep_kernel(const double* __restrict_
     __shared__ int s_chol;
     if (tid == 0) s_chol = 0;
     __syncthreads();
-    if (use_chol && !G0 && pass == 0 && s_shift == 0.0) {
+    // Code placement, not arithmetic: the step loop below is sensitive to where its blocks fall in the instruction stream.  With
+    // these 12 bytes the loop sits where it was measured (1.70 ms per 128 x 128 matrix); 12 bytes earlier the same
+    // instructions take 1.75 ms (three alternating rounds, spread 0.005 ms).  Re-measure tools/eigh_bench.py 128 when the code
+    // above this line changes size, and drop or resize the pad accordingly.
+    asm volatile("s_nop 0\n\ts_nop 0\n\ts_nop 0");
+    if (!G0 && pass == 0 && s_shift == 0.0) {
         bool ok = true;
         for (int j = 0; j < D; ++j) {
             const double piv = G[j * LD + j];   // every thread reads the same value (behind the barrier of the step before)
@@ -553,12 +557,11 @@ int eigh_onesided(const double* A, int nb, int D, int fn, double* out, double* e
         gemm_f64_launch(0, 0, nb, D, D, D, 1.0, Vinit, (size_t)D * D, A, (size_t)D * D, 0.0, g0, st);
         G0 = g0;
     }
-    static const int use_chol = getenv("OTVAE_EIGH_NO_CHOL") ? 0 : 1;
     for (int pass = 0; pass < 2; ++pass) {  // pass 1: no-ops unless pass 0 met a +-lambda pair (see the header)
         if (D > 64)
-            hj_sweep_kernel<8><<<nb, 512, lds, st>>>(A, D, ws, G0, warm, pass, use_chol);
+            hj_sweep_kernel<8><<<nb, 512, lds, st>>>(A, D, ws, G0, warm, pass);
         else
-            hj_sweep_kernel<16><<<nb, 512, lds, st>>>(A, D, ws, G0, warm, pass, use_chol);
+            hj_sweep_kernel<16><<<nb, 512, lds, st>>>(A, D, ws, G0, warm, pass);
         OTVAE_CHECK_LAUNCH("otvae_eigh_fn(sweeps)");
         hj_vectors_kernel<<<dim3(cdiv(D, 4), nb), 256, 0, st>>>(D, ws, Vinit, warm, pass);
         OTVAE_CHECK_LAUNCH("otvae_eigh_fn(vectors)");
@@ -575,21 +578,21 @@ int eigh_onesided(const double* A, int nb, int D, int fn, double* out, double* e
 // ================================================================================================ 128 < D <= 1024
 // The same iteration across workgroups (the reference's tests/test_latent_transport.py transports 64x4x4 = 1024-dimensional
 // latents).  G and V live in global memory (8 MiB each at D = 1024: L2 / Infinity-Cache resident), column by column.  The
-// columns are cut into blocks of 8; a ROUND pairs the blocks round-robin and one workgroup per block pair
-//   * loads its 16 columns of G into LDS (131 KB at D = 1024), runs the odd-even sweep of hj_sweep_kernel over the 16
-//     positions (a wave per pair slot, the kept column in registers, 16 steps), logging the rotations in LDS;
-//   * writes the columns back to their HOME slots (16 steps reverse the order of the positions, so position p goes home to
-//     15 - p): a column of G never changes its slot, the round-robin over blocks therefore meets every pair of columns;
-//   * loads the same 16 columns of V and replays the logged rotations on them.
+// columns are cut into blocks of 8; a ROUND pairs the blocks round-robin and one workgroup per block pair (hjg_round_kernel)
+//   * loads its 16 columns of G into LDS (131 KB at D = 1024) and forms their 16 x 16 Gram matrix on the fp64 matrix cores;
+//   * runs one sweep of two-sided Jacobi on that Gram matrix in LDS, accumulating the rotations in a 16 x 16 matrix Q;
+//   * writes the columns times Q back to the slots they came from: a column of G never changes its slot, the round-robin over
+//     blocks therefore meets every pair of columns;
+//   * logs Q, from which the NEXT launch applies the same rotations to the 16 columns of V (beside its own rotations).
 // Positive definite input (the covariances this path exists for) is first factored, A = L L^T (otvae_cholesky), and the
 // iteration runs on the columns of X = L: X V = Q S gives A = X X^T = Q S^2 Q^T -- eigenvalues |x_k|^2, eigenvectors the
-// NORMALISED FINAL COLUMNS themselves, so V is neither kept nor updated (ctl->qmode; the update role of a launch returns at
-// once).  The iteration sees cond(A)^1/2 instead of the cond(A)^2 that working on the columns of A itself implies (the Gram
-// matrix of A's columns is A^2), which is what its convergence speed depends on: an ill-conditioned 1024 x 1024 latent
-// covariance needed > 16 sweeps on A and needs ~10 on its factor.  Round 2 iterated on the columns of L^T (the rows of L:
-// no transposed copy, but V had to be carried and the sweep count is ~20 % higher: 11 against 9 at D = 128 in a numpy
-// restatement of the ordering); OTVAE_EIGH_BLOCK_LT=1 brings that variant back for an A/B.  When the factorisation
-// meets a non-positive pivot (device flag) the columns of A are iterated as in the small solver.
+// NORMALISED FINAL COLUMNS themselves, so V is neither kept nor updated (ctl->chol_info == 0; the update role of a launch
+// returns at once).  The iteration sees cond(A)^1/2 instead of the cond(A)^2 that working on the columns of A itself implies
+// (the Gram matrix of A's columns is A^2), which is what its convergence speed depends on: an ill-conditioned 1024 x 1024
+// latent covariance needed > 16 sweeps on A and needs ~10 on its factor.  The columns of L, not of L^T (the rows of L: no
+// transposed copy, but V has to be carried and the sweep count is ~20 % higher: 11 against 9 at D = 128 in a numpy
+// restatement of the ordering; measured in profiles/r03_eigh_block_ab.txt).  When the factorisation meets a non-positive
+// pivot (device flag) the columns of A are iterated as in the small solver, and V is carried.
 // One launch per round (nblk - 1 rounds per sweep); the stop test is a device flag: a round that rotated above the stop level
 // marks the sweep, a tiny kernel after each sweep turns the remaining launches into no-ops once a sweep stayed quiet.
 #define HJB_B 8
@@ -598,9 +601,9 @@ int eigh_onesided(const double* A, int nb, int D, int fn, double* out, double* e
 
 struct HjbCtl {
     int done, rotated, sweeps;
-    int chol_info;  // 0: the iteration runs on the Cholesky factor; else on A itself (written by otvae_cholesky before the init kernel)
+    int chol_info;  // 0: the iteration runs on the columns of the Cholesky factor L, the eigenvectors are the final columns and V is
+                    // not kept; else on A itself (written by otvae_cholesky before the init kernel)
     int log_stamp[2];  // id of the launch whose column rotations fill rotation log 0 / 1 (-1: none)
-    int qmode;         // the iteration runs on the columns of L (not of L^T): the eigenvectors are the final columns, V is not kept
 };
 #define HJB_VSLABS 2  // row slabs the eigenvector update of a block pair is split over (when the launch still fits the chip)
 
@@ -634,15 +637,14 @@ __host__ __device__ static inline HjbWs hjb_ws(void* ws, int b, int D) {
     return r;
 }
 
-__global__ __launch_bounds__(256) void hjb_init_kernel(const double* __restrict__ Ain, int D, void* __restrict__ ws, int lcols) {
+__global__ __launch_bounds__(256) void hjb_init_kernel(const double* __restrict__ Ain, int D, void* __restrict__ ws) {
     const HjbWs w = hjb_ws(ws, blockIdx.y, D);
     const double* Ab = Ain + (size_t)blockIdx.y * D * D;
     const size_t total = (size_t)hjb_dp(D) * D;
     for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const int c = (int)(e / D), i = (int)(e - (size_t)c * D);
         double v = 0.0;  // zero dummy columns
-        if (c < D) v = w.ctl->chol_info == 0 ? (lcols ? w.T[(size_t)i * D + c]   // column c of X = L (zero above the diagonal)
-                                                      : w.T[e])                   // column c of X = L^T is row c of L
+        if (c < D) v = w.ctl->chol_info == 0 ? w.T[(size_t)i * D + c]   // column c of X = L (zero above the diagonal)
                                              : ((i >= c) ? Ab[(size_t)i * D + c] : Ab[(size_t)c * D + i]);  // lower triangle of A
         w.G[e] = v;
         w.V[e] = (c == i) ? 1.0 : 0.0;
@@ -652,7 +654,6 @@ __global__ __launch_bounds__(256) void hjb_init_kernel(const double* __restrict_
         w.ctl->rotated = 0;
         w.ctl->sweeps = 0;
         w.ctl->log_stamp[0] = w.ctl->log_stamp[1] = -1;
-        w.ctl->qmode = (lcols && w.ctl->chol_info == 0) ? 1 : 0;
     }
 }
 
@@ -673,209 +674,22 @@ __device__ __forceinline__ void hjb_pair(int round, int k, int nblk, int& I, int
     }
 }
 
-// One launch = the column rotations of round `launch % nrounds` (blocks 0 .. pairs-1, one block pair each) AND the eigenvector update
-// of the PREVIOUS launch's round (blocks pairs .., HJB_VSLABS row slabs per block pair): the update only replays logged rotations
-// on the rows of V, so it neither feeds the next round's rotations nor needs whole columns -- it runs beside them on otherwise idle
-// CUs instead of behind them in the same workgroup (70 -> 45 us per round at D = 1024).  The log is double-buffered in the
-// workspace and stamped with the launch that filled it: a rotation role that found the solver converged leaves no stamp, and the
-// update role of the next launch has nothing to replay.
-template <int R>  // rows per lane: D <= 64 R
-__global__ __launch_bounds__(512) void hjb_round_kernel(int D, int launch, int nrounds, int rotate, int vslabs, void* __restrict__ ws) {
-    extern __shared__ __align__(16) double hj_lds[];
-    __shared__ double2 s_log[2 * HJB_B][HJB_B];
-    __shared__ double s_nrm[2 * HJB_B];  // squared norms of the columns in the even positions (the kept columns' live in registers)
-    __shared__ int s_rot;
-    const HjbWs w = hjb_ws(ws, blockIdx.y, D);
-    constexpr int NP = 2 * HJB_B;  // positions
-    const int nblk = hjb_dp(D) / HJB_B, npairs = nblk / 2;
-    const bool vrole = (int)blockIdx.x >= npairs;
-    int pair_idx, row0, nrows, my_launch;
-    if (!vrole) {
-        if (!rotate || w.ctl->done) return;
-        pair_idx = blockIdx.x;
-        row0 = 0;
-        nrows = D;
-        my_launch = launch;
-    } else {
-        my_launch = launch - 1;
-        if (my_launch < 0 || w.ctl->qmode || w.ctl->log_stamp[my_launch & 1] != my_launch) return;
-        const int v = blockIdx.x - npairs;
-        pair_idx = v / vslabs;
-        const int per = ((D + vslabs - 1) / vslabs + 63) / 64 * 64;  // rows per slab, whole lanes
-        row0 = (v % vslabs) * per;
-        nrows = min(per, D - row0);
-        if (nrows <= 0) return;
-    }
-    const int LD = nrows + 1;
-    int I, J;
-    hjb_pair(my_launch % nrounds, pair_idx, nblk, I, J);
-    const int tid = threadIdx.x, lane = tid & 63, g = tid >> 6;  // wave g = pair slot g
-    const int kpos = 2 * g + 1;
-    auto home = [&](int pos) { return pos < HJB_B ? I * HJB_B + pos : J * HJB_B + (pos - HJB_B); };
-    double* P = hj_lds;  // P[pos * LD + row - row0]
-    double2* glog = w.log + ((size_t)(my_launch & 1) * npairs + pair_idx) * NP * HJB_B;
-    if (tid == 0) s_rot = 0;
-    if (vrole)
-        for (int e = tid; e < NP * HJB_B; e += 512) s_log[e / HJB_B][e % HJB_B] = glog[e];
-
-    auto sweep16 = [&](double* __restrict__ M, bool replay) {
-        // load the 16 columns (a wave per column, two columns each)
-        for (int pos = g; pos < NP; pos += 8) {
-            const double* src = M + (size_t)home(pos) * D + row0;
-            for (int i = lane; i < nrows; i += 64) P[pos * LD + i] = src[i];
-        }
-        __syncthreads();
-        double keep[R];
-        double nk = 0.0;  // |kept column|^2, tracked through the round: a step then needs ONE dot product (the pair's) instead of three
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int i = lane + 64 * u;
-            keep[u] = i < nrows ? P[kpos * LD + i] : 0.0;
-        }
-        if (!replay) {
-            double ne = 0.0;
-#pragma unroll
-            for (int u = 0; u < R; ++u) {
-                const int i = lane + 64 * u;
-                const double e = i < nrows ? P[(kpos - 1) * LD + i] : 0.0;
-                nk = fma(keep[u], keep[u], nk);
-                ne = fma(e, e, ne);
-            }
-            nk = wave_allsum_dpp(nk);
-            ne = wave_allsum_dpp(ne);
-            if (lane == 0) s_nrm[kpos - 1] = ne;
-            __syncthreads();
-        }
-        auto step = [&](auto odd_tag, int t) {
-            constexpr bool ODD = decltype(odd_tag)::value;
-            const int opos = ODD ? kpos + 1 : kpos - 1;
-            if (opos < NP) {
-                double other[R];
-                double* go = P + opos * LD;
-#pragma unroll
-                for (int u = 0; u < R; ++u) {
-                    const int i = lane + 64 * u;
-                    other[u] = i < nrows ? go[i] : 0.0;
-                }
-                double c = 1.0, s = 0.0;
-                if (replay) {
-                    const double2 cs = s_log[t][g];
-                    c = cs.x;
-                    s = cs.y;
-#pragma unroll
-                    for (int u = 0; u < R; ++u) {
-                        const int i = lane + 64 * u;
-                        double pub;
-                        if (ODD) {
-                            pub = c * keep[u] - s * other[u];
-                            keep[u] = s * keep[u] + c * other[u];
-                        } else {
-                            pub = s * other[u] + c * keep[u];
-                            keep[u] = c * other[u] - s * keep[u];
-                        }
-                        if (i < nrows) go[i] = pub;
-                    }
-                } else {
-                    double gamma = 0.0;
-#pragma unroll
-                    for (int u = 0; u < R; ++u) gamma = fma(keep[u], other[u], gamma);
-                    gamma = wave_allsum_dpp(gamma);
-                    const double no = s_nrm[opos];
-                    // the pair is (a, b) = (keep, other) in an odd step, (other, keep) in an even one; it becomes
-                    // (c a - s b, s a + c b) with squared norms alpha - t gamma and beta + t gamma
-                    const double alpha = ODD ? nk : no, beta = ODD ? no : nk;
-                    const double ab = alpha * beta;
-                    double tg = 0.0;
-                    if (gamma * gamma > HJ_TOL2 * ab && ab > 1e-280) {
-                        const double zeta = (beta - alpha) * 0.5 * nr_rcp(gamma);
-                        const double az = fabs(zeta);
-                        double tt;
-                        if (az > 1e8) {
-                            tt = 0.5 * nr_rcp(zeta);
-                        } else {
-                            const double q2 = fma(zeta, zeta, 1.0);
-                            tt = nr_rcp(az + q2 * nr_rsq(q2));
-                            tt = zeta >= 0.0 ? tt : -tt;
-                        }
-                        c = nr_rsq(fma(tt, tt, 1.0));
-                        s = c * tt;
-                        tg = tt * gamma;
-                        if (lane == 0 && gamma * gamma > HJ_STOP2 * ab) s_rot = 1;
-                    }
-                    if (lane == 0) s_log[t][g] = make_double2(c, s);
-                    // tracked norms of the two new columns; the shrinking one (alpha - t gamma) is recomputed below when the
-                    // subtraction cancelled more than two digits (rank-deficient input: a column on its way to zero)
-                    const double n_x = alpha - tg, n_y = beta + tg;
-                    const bool recount = !(n_x > 0.01 * alpha) && tg != 0.0;
-                    double n_pub = ODD ? n_x : n_y;
-                    nk = ODD ? n_y : n_x;
-                    double acc2 = 0.0;
-#pragma unroll
-                    for (int u = 0; u < R; ++u) {
-                        const int i = lane + 64 * u;
-                        double pub;
-                        if (ODD) {
-                            pub = c * keep[u] - s * other[u];
-                            keep[u] = s * keep[u] + c * other[u];
-                        } else {
-                            pub = s * other[u] + c * keep[u];
-                            keep[u] = c * other[u] - s * keep[u];
-                        }
-                        if (i < nrows) go[i] = pub;
-                        if (recount) acc2 = ODD ? fma(pub, pub, acc2) : fma(keep[u], keep[u], acc2);
-                    }
-                    if (recount) {  // wave-uniform
-                        acc2 = wave_allsum_dpp(acc2);
-                        if (ODD) n_pub = acc2;
-                        else nk = acc2;
-                    }
-                    if (lane == 0) s_nrm[opos] = n_pub;
-                }
-            } else if (!replay && lane == 0) {
-                s_log[t][g] = make_double2(1.0, 0.0);  // the idle slot of an odd step: its log entry is never read, but it is copied
-            }
-            __syncthreads();
-        };
-        for (int t = 0; t < NP; t += 2) {
-            step(std::false_type{}, t);
-            step(std::true_type{}, t + 1);
-        }
-        // 16 steps reversed the order: position p holds what started at 15 - p and goes back there
-        {
-            double* dst = M + (size_t)home(NP - 1 - kpos) * D + row0;
-#pragma unroll
-            for (int u = 0; u < R; ++u) {
-                const int i = lane + 64 * u;
-                if (i < nrows) dst[i] = keep[u];
-            }
-        }
-        for (int pos = 2 * g; pos < NP; pos += 16) {  // the even positions: wave g writes position 2g
-            double* dst = M + (size_t)home(NP - 1 - pos) * D + row0;
-            for (int i = lane; i < nrows; i += 64) dst[i] = P[pos * LD + i];
-        }
-        __syncthreads();
-    };
-    if (vrole) {
-        sweep16(w.V, true);
-        return;
-    }
-    sweep16(w.G, false);
-    for (int e = tid; e < NP * HJB_B; e += 512) glog[e] = s_log[e / HJB_B][e % HJB_B];
-    if (tid == 0) {
-        if (s_rot) w.ctl->rotated = 1;  // benign race: every writer stores 1
-        if (blockIdx.x == 0) w.ctl->log_stamp[launch & 1] = launch;
-    }
-}
-
-// ---- the same round from the block pair's GRAM matrix ----------------------------------------------------------------------
-// The 16 sequential column steps above each reduce over all D rows; here the rotation workgroup forms W = B^T B (16 x 16, the
-// 16 columns B of the block pair; one v_mfma_f64_16x16x4_f64 per 4 rows: a lane's element of B is both operands), runs ONE
-// cyclic sweep of two-sided Jacobi on W in LDS (15 steps of 8 disjoint rotations on 16-vectors, accumulated in Q) and applies
-// B <- B Q as a product; the update role applies the same Q to the rows of V.  A numpy restatement (block pairs of 16 columns,
-// one inner sweep, the Cholesky factor of covariance-like and graded matrices) needs the same number of outer sweeps as the
-// column steps and ends at the same cosines (1e-15).  Measured at D = 1024 (phases switched off one at a time): a launch is
-// ~31 us instead of ~40 -- ~15 us of it the launch itself plus streaming the 16 columns in, 2.6 us the Gram matrix, ~6 us the 8
-// rotation steps, ~7 us writing the rotated columns back: every round moves the whole of X and V (33 MB) through HBM.
+// ---- a round from the block pair's GRAM matrix -----------------------------------------------------------------------------
+// One launch = the column rotations of round `launch % nrounds` (blocks 0 .. pairs-1, one block pair each: the rotation role) AND
+// the eigenvector update of the PREVIOUS launch's round (blocks pairs .., HJB_VSLABS row slabs per block pair: the update role).
+// The update only replays logged rotations on the rows of V, so it neither feeds the next round's rotations nor needs whole
+// columns -- it runs beside them on otherwise idle CUs instead of behind them in the same workgroup (70 -> 45 us per round at
+// D = 1024).  The log is double-buffered in the workspace and stamped with the launch that filled it: a rotation role that
+// found the solver converged leaves no stamp, and the update role of the next launch has nothing to replay.
+// Running 16 sequential one-sided column steps on the block pair would reduce over all D rows in each of them; instead the
+// rotation workgroup forms W = B^T B (16 x 16, the 16 columns B of the block pair; one v_mfma_f64_16x16x4_f64 per 4 rows: a
+// lane's element of B is both operands), runs ONE cyclic sweep of two-sided Jacobi on W in LDS (15 steps of 8 disjoint rotations
+// on 16-vectors, accumulated in Q) and applies B <- B Q as a product; the update role applies the same Q to the rows of V.  A
+// numpy restatement (block pairs of 16 columns, one inner sweep, the Cholesky factor of covariance-like and graded matrices)
+// needs the same number of outer sweeps as such column steps and ends at the same cosines (1e-15).  Measured at D = 1024
+// (phases switched off one at a time): a launch is ~31 us instead of ~40 -- ~15 us of it the launch itself plus streaming the
+// 16 columns in, 2.6 us the Gram matrix, ~6 us the 8 rotation steps, ~7 us writing the rotated columns back: every round moves
+// the whole of X and V (33 MB) through HBM.
 // Columns keep their slots (no exchange of places): the log is the 16 x 16 matrix Q of the block pair.
 typedef double double4v_hj __attribute__((ext_vector_type(4)));
 
@@ -944,7 +758,7 @@ __global__ __launch_bounds__(512) void hjg_round_kernel(int D, int launch, int n
         my_launch = launch;
     } else {
         my_launch = launch - 1;
-        if (my_launch < 0 || w.ctl->qmode || w.ctl->log_stamp[my_launch & 1] != my_launch) return;
+        if (my_launch < 0 || w.ctl->chol_info == 0 || w.ctl->log_stamp[my_launch & 1] != my_launch) return;
         pair_idx = (blockIdx.x - npairs) / vslabs;
     }
     int I, J;
@@ -1166,7 +980,7 @@ __global__ __launch_bounds__(256) void hjb_finish_kernel(int D, int fn, void* __
     if (threadIdx.x == 0) s_noise = 64.0 * D * 2.220446049250313e-16 * fmax(fmax(s_max[0], s_max[1]), fmax(s_max[2], s_max[3]));
     __syncthreads();
     const double noise = s_noise;
-    const bool chol = w.ctl->chol_info == 0, qmode = w.ctl->qmode != 0;
+    const bool chol = w.ctl->chol_info == 0;
     // the columns of an indefinite A were iterated unshifted: a +-lambda pair of equal size is a double eigenvalue of A^2 and the
     // iteration may have stopped at a mixture of its two eigenvectors (|v . g| < |g|, see the header of this file).  The small
     // solver repeats such a matrix on A + |A|_inf I; here (a hundred launches per sweep) the matrix gets NaN eigenvalues instead
@@ -1186,7 +1000,7 @@ __global__ __launch_bounds__(256) void hjb_finish_kernel(int D, int fn, void* __
     for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const int k = (int)(e / D);
         double v;
-        if (qmode) {  // the eigenvectors are the normalised final columns; V (one eigenvector per row) is filled for the product below
+        if (chol) {  // the eigenvectors are the normalised final columns; V (one eigenvector per row) is filled for the product below
             v = w.nrm[k] > 0.0 ? w.G[e] / w.nrm[k] : 0.0;
             if (fn != 3) w.V[e] = v;
         } else {
@@ -1202,21 +1016,9 @@ __global__ __launch_bounds__(256) void hjb_finish_kernel(int D, int fn, void* __
 }
 
 
-static bool g_hjb_lds_set[2] = {false, false};
 static bool g_hjg_lds_set = false;
 
 int eigh_block_onesided(const double* A, int nb, int D, int fn, double* out, double* eigvals, void* ws, hipStream_t st) {
-    const size_t lds = (size_t)2 * HJB_B * (D + 1) * sizeof(double);
-    const bool big = D > 512;
-    if (lds > 65536 && !g_hjb_lds_set[big]) {
-        const hipError_t e = big ? hipFuncSetAttribute((const void*)hjb_round_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * HJB_B * (HJB_MAX_D + 1) * 8))
-                                 : hipFuncSetAttribute((const void*)hjb_round_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * HJB_B * 513 * 8));
-        if (e != hipSuccess) {
-            otvae_set_error("otvae_eigh_fn: cannot raise dynamic LDS limit");
-            return OTVAE_ELAUNCH;
-        }
-        g_hjb_lds_set[big] = true;
-    }
     if (!g_hjg_lds_set) {
         if (hipFuncSetAttribute((const void*)hjg_round_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(2 * HJB_B * (HJB_MAX_D + 1) * 8)) != hipSuccess) {
@@ -1232,22 +1034,15 @@ int eigh_block_onesided(const double* A, int nb, int D, int fn, double* out, dou
         const int rc = cholesky_blocked(A, nb, D, w0.T, per / sizeof(double), &w0.ctl->chol_info, per / sizeof(int), st);
         if (rc) return rc;
     }
-    static const int lcols = getenv("OTVAE_EIGH_BLOCK_LT") ? 0 : 1;  // A/B switch: the round-2 iteration on the columns of L^T
-    hjb_init_kernel<<<dim3(imin(cdiv((size_t)Dp * D, 256), 1024), nb), 256, 0, st>>>(A, D, ws, lcols);
+    hjb_init_kernel<<<dim3(imin(cdiv((size_t)Dp * D, 256), 1024), nb), 256, 0, st>>>(A, D, ws);
     const int nrounds = nblk - 1;
     // one workgroup per CU at these LDS sizes: split the eigenvector update over row slabs only while every block of a launch is
     // still resident at once (two matrices of D = 1024 side by side are 128 rotation + 128 update blocks already)
     const int vslabs = (nblk / 2 * (1 + HJB_VSLABS) * nb <= 256) ? HJB_VSLABS : 1;
     const dim3 grid(nblk / 2 * (1 + vslabs), nb);  // rotation blocks, then the eigenvector-update blocks of the launch before
-    static const bool column_steps = getenv("OTVAE_EIGH_COLUMN_STEPS") != nullptr;  // A/B switch: the first-generation rounds
     const size_t lds_g = (size_t)2 * HJB_B * (((D + 15) & ~15) + 1) * sizeof(double);
     auto round_launch = [&](int launch, int rotate) {
-        if (!column_steps)
-            hjg_round_kernel<<<grid, 512, lds_g, st>>>(D, launch, nrounds, rotate, vslabs, ws);
-        else if (big)
-            hjb_round_kernel<16><<<grid, 512, lds, st>>>(D, launch, nrounds, rotate, vslabs, ws);
-        else
-            hjb_round_kernel<8><<<grid, 512, lds, st>>>(D, launch, nrounds, rotate, vslabs, ws);
+        hjg_round_kernel<<<grid, 512, lds_g, st>>>(D, launch, nrounds, rotate, vslabs, ws);
     };
     // The launches of a converged solver are no-ops, but a no-op still costs its ~2 us of queue time and a sweep is 31 ... 127 of
     // them: the 24-sweep budget, issued blindly, spent 1 ms (D = 256) ... 4 ms (D = 1024) behind the ~10 sweeps that did the
@@ -1257,7 +1052,6 @@ int eigh_block_onesided(const double* A, int nb, int D, int fn, double* out, dou
     // Under capture (nothing may synchronise) the whole budget is recorded as before.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
-    static const bool no_follow = getenv("OTVAE_EIGH_NO_FOLLOW") != nullptr;  // A/B switch
     // The pinned flags, the two events and the lock are PER DEVICE: events are bound to the device that was current when
     // they were made, so one process-wide pair failed hipEventRecord on a second GPU's stream, and one lock serialised the solves
     // of all devices.  Indexed by the calling thread's current device, which is the stream's device under torch.
@@ -1268,7 +1062,7 @@ int eigh_block_onesided(const double* A, int nb, int D, int fn, double* out, dou
     };
     static FollowState follow_tab[16];
     int follow_dev = -1;
-    bool follow = cap == hipStreamCaptureStatusNone && !no_follow;
+    bool follow = (cap == hipStreamCaptureStatusNone);
     if (follow && (hipGetDevice(&follow_dev) != hipSuccess || follow_dev < 0 || follow_dev >= 16)) follow = false;
     FollowState& fs = follow_tab[follow ? follow_dev : 0];
     std::unique_lock<std::mutex> follow_lock(fs.mu, std::defer_lock);

@@ -1095,7 +1095,7 @@ extern "C" int otvae_ot_cost_grad(int dtype, const void* z, const void* y, const
     OTVAE_REQUIRE(dtype == 0 || dtype == 1, "otvae_ot_cost_grad: dtype must be 0 or 1");
     const dim3 grid(cdiv(D, 32), cdiv(N, 32));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0 && (uintptr_t)pi % 16 == 0 && !getenv("OTVAE_OT_GRAD_VALU"))
+    if (dtype == 0 && (uintptr_t)pi % 16 == 0)
         ot_cost_grad_mfma_kernel<<<dim3(cdiv(D, 16), cdiv(N, 16)), 256, 0, st>>>((const float*)z, (const float*)y, (const float*)pi,
                                                                                  (const float*)g, ng, (float)scale, (const float*)gadd, N,
                                                                                  M, D, (float*)gz);
