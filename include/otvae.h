@@ -699,6 +699,27 @@ int otvae_poly_mmd_subsets(const float* real, int64_t n_real, const float* fake,
  * rows stored, rows seen) is read on the device -- a captured call appends at the right place on every replay -- and advanced by a
  * single-thread launch behind the copy: stored = min(stored + B, capacity), seen += B. */
 int otvae_feature_append(int in_dtype, const void* feats, int B, int D, float* buf, int64_t capacity, int64_t* count, void* stream);
+/* k-nearest-neighbour manifold statistics (csrc/knn_manifold.hip; metrics/prdc.py): the pieces of improved precision / recall and of
+ * density / coverage.  Features fp32 row-major, distances d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 <a, b>) in fp64 on the fp64 matrix
+ * cores (the tile of otvae_poly_mmd_subsets), the same bits for a pair in every call and whichever side a row is on.  Outputs are
+ * order statistics, integer counts and minima: bit-identical from run to run.  Balls are closed (<=).  Finite features are a
+ * precondition; nothing of size n x n is in memory.
+ * otvae_knn_sq_radii: r2[i] = the k-th smallest of { d2(x_i, x_j) : j != i } -- self is excluded by INDEX: a duplicate row is a neighbour
+ *   at distance 0.  x [n][D], r2 [n] fp64.  The nt = ceil(n / 128) column tiles of a 128-row strip are split over otvae_knn_groups(n)
+ *   workgroups (the smallest G <= min(nt, 2^25 / n) that minimises ceil(nt G / 512) ceil(nt / G): rounds of resident workgroups times
+ *   tiles per workgroup), each leaving its k candidates per row in ws; a second launch merges them.
+ *   ws: otvae_knn_sq_radii_ws(n, D, k) bytes = 8 (n + groups n k).
+ * otvae_manifold_counts: with d2_ij = d2(real_i, fake_j): count_fake[j] = #{ i : d2_ij <= r2_real[i] } (int32 [n_fake]),
+ *   hit_real[i] = 1 if some j has d2_ij <= r2_fake[j], else 0 (int32 [n_real]), min_real[i] = min_j d2_ij (fp64 [n_real]).  Per-tile
+ *   partials in ws, combined by a second launch.  ws: otvae_manifold_counts_ws(n_real, n_fake, D) bytes.
+ * OTVAE_EINVAL, nothing launched (the _ws queries and otvae_knn_groups: -1): null pointers, k outside 1 .. 16, n <= k (counts: n < 2),
+ * D outside 1 .. 2048, n > 2^21. */
+int otvae_knn_groups(int64_t n);
+int64_t otvae_knn_sq_radii_ws(int64_t n, int D, int k); /* bytes; -1: refused arguments */
+int64_t otvae_manifold_counts_ws(int64_t n_real, int64_t n_fake, int D); /* bytes; -1: refused arguments */
+int otvae_knn_sq_radii(const float* x, int64_t n, int D, int k, double* r2, void* ws, void* stream);
+int otvae_manifold_counts(const float* real, const double* r2_real, int64_t n_real, const float* fake, const double* r2_fake,
+                          int64_t n_fake, int D, int32_t* count_fake, int32_t* hit_real, double* min_real, void* ws, void* stream);
 
 /* ---- symmetric eigen-decomposition based matrix functions (ot/matrix_utils.py:37-109) --------------------- */
 /* A[nb][D][D] fp64 symmetric (lower triangle is read, like eigh(UPLO='L')).  fn: 0 = none (eigvals only),

@@ -178,6 +178,11 @@ SIGNATURES = {
     "otvae_poly_mmd_ws": (i64, [i32, i32, i32]),
     "otvae_poly_mmd_subsets": (i32, [vp, i64, vp, i64, i32, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp]),
     "otvae_feature_append": (i32, [i32, vp, i32, i32, vp, i64, vp, vp]),
+    "otvae_knn_groups": (i32, [i64]),
+    "otvae_knn_sq_radii_ws": (i64, [i64, i32, i32]),
+    "otvae_manifold_counts_ws": (i64, [i64, i64, i32]),
+    "otvae_knn_sq_radii": (i32, [vp, i64, i32, i32, vp, vp, vp]),
+    "otvae_manifold_counts": (i32, [vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
     "otvae_eigh_ws": (i64, [i32, i32]),
     "otvae_eigh_onesided_ws": (i64, [i32, i32]),
     "otvae_eigh_block_onesided_ws": (i64, [i32, i32]),

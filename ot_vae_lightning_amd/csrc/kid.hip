@@ -10,7 +10,7 @@
 //   * a workgroup of 4 waves; wave (wr, wc) owns the 64 x 64 quarter (wr, wc) of the tile as 4 x 4 v_mfma_f64_16x16x4_f64 accumulators
 //     (operand / result layout as in metrics.hip: lane l supplies A[l % 16][l / 16] and B[l / 16][l % 16], register r of lane l holds
 //     D[4 r + l / 16][l % 16]): 8 LDS reads feed 16 MFMAs.
-//   * the features are walked in chunks of 32: both gathered 128 x 32 row panels (one on a diagonal tile) go through LDS once per
+//   * (this and the item above are gram_tile.h, which knn_manifold.hip shares) the features are walked in chunks of 32: both gathered 128 x 32 row panels (one on a diagonal tile) go through LDS once per
 //     chunk, converted to fp64 while staged.  The gather is at the load: a thread reads real[idx[row]][k0 + k ...], 8 lanes one
 //     128-byte row segment with 16-byte loads (D a multiple of 4, 16-byte aligned bases: 11 % faster at D = 2048 than the 4-byte
 //     form, which remains for every other D, 32 lanes per segment); no [S][m][D] array ever exists.  LDS is row-major with a row stride of 34 doubles (68 dwords = 4 mod 64
@@ -27,12 +27,11 @@
 //   * a second launch (one workgroup per subset) adds the subset's partials in index order into per_subset; a third (one workgroup)
 //     forms stats = {mean (summed in double-double), population std (two passes about per_subset[0])}.
 // otvae_feature_append -- rows to buf[count[0] ...], the offset read on the device; a single-thread launch then advances the counts.
-#include "common.h"
+#include "gram_tile.h"
 
-#define PM_T 128             // output tile
-#define PM_KC 32             // features per staged chunk
-#define PM_LD 34             // LDS row stride (doubles)
-#define PM_MAX_D 2048
+#define PM_T GT_T           // output tile, LDS row stride and the widest features: the shared tile's (gram_tile.h)
+#define PM_LD GT_LD
+#define PM_MAX_D GT_MAX_D
 #define PM_MAX_DEGREE 8
 #define PM_MAX_S 65535
 
@@ -94,7 +93,6 @@ __global__ __launch_bounds__(256, 2) void pm_tile_kernel(const float* __restrict
     const int32_t* ia = kind == 1 ? idx_fake : idx_real;
     const int32_t* ib = kind == 0 ? idx_real : idx_fake;
     const int64_t na = kind == 1 ? n_fake : n_real, nb = kind == 0 ? n_real : n_fake;
-    double (*bs)[PM_LD] = diag ? as : bs_;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, lk = lane >> 4;
@@ -123,76 +121,7 @@ __global__ __launch_bounds__(256, 2) void pm_tile_kernel(const float* __restrict
     __syncthreads();
 
     f64x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-    // staging of a 128 x 32 panel, 16 floats per thread.  VEC (D a multiple of 4, 16-byte aligned bases): thread (row = tid / 8 + 32 u,
-    // k = 4 (tid % 8)) loads 16 bytes, 8 lanes one 128-byte row segment; otherwise thread (row = tid / 32 + 8 u, k = tid % 32) loads 4
-    const int sk = VEC ? (tid & 7) * 4 : tid & 31, sr = VEC ? tid >> 3 : tid >> 5;
-    float ra[PM_T / 8], rb[PM_T / 8];
-    auto fetch = [&](int k0) {
-        const bool k_ok = k0 + sk < D;
-        if (VEC) {
-#pragma unroll
-            for (int u = 0; u < PM_T / 32; ++u) {
-                const int64_t oa = row_a[sr + 32 * u];
-                const f32x4 va = (k_ok && oa >= 0) ? *reinterpret_cast<const f32x4*>(pa + oa + k0 + sk) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ra[4 * u + e] = va[e];
-                if (!diag) {
-                    const int64_t ob = row_b[sr + 32 * u];
-                    const f32x4 vb = (k_ok && ob >= 0) ? *reinterpret_cast<const f32x4*>(pb + ob + k0 + sk) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) rb[4 * u + e] = vb[e];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < PM_T / 8; ++u) {
-                const int64_t oa = row_a[sr + 8 * u];
-                ra[u] = (k_ok && oa >= 0) ? pa[oa + k0 + sk] : 0.f;
-                if (!diag) {
-                    const int64_t ob = row_b[sr + 8 * u];
-                    rb[u] = (k_ok && ob >= 0) ? pb[ob + k0 + sk] : 0.f;
-                }
-            }
-        }
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < D; k0 += PM_KC) {
-        if (VEC) {
-#pragma unroll
-            for (int u = 0; u < PM_T / 32; ++u)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    as[sr + 32 * u][sk + e] = (double)ra[4 * u + e];
-                    if (!diag) bs_[sr + 32 * u][sk + e] = (double)rb[4 * u + e];
-                }
-        } else {
-#pragma unroll
-            for (int u = 0; u < PM_T / 8; ++u) {
-                as[sr + 8 * u][sk] = (double)ra[u];
-                if (!diag) bs_[sr + 8 * u][sk] = (double)rb[u];
-            }
-        }
-        __syncthreads();
-        if (k0 + PM_KC < D) fetch(k0 + PM_KC);   // in flight under the MFMAs below
-#pragma unroll
-        for (int ks = 0; ks < PM_KC / 4; ++ks) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) av[a] = as[wr * 64 + a * 16 + l16][ks * 4 + lk];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) bv[b] = bs[wc * 64 + b * 16 + l16][ks * 4 + lk];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a], bv[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    gram_tile_mma<VEC>(pa, pb, row_a, row_b, D, diag, as, bs_, acc);   // gram_tile.h: staging and the MFMA main loop
 
     // epilogue: k, masks, transposition-invariant sums (header)
     const int src_hi = (l16 & 3) * 16 + lk;   // lane holding the transposed element of register r: src_hi + 4 r, its register l16 / 4

@@ -5,15 +5,13 @@ random subsets.  Unlike the Frechet distance it is usable from a few dozen sampl
 The metric keeps the features themselves (fp32, a fixed-size buffer per side, appended to by ``otvae_feature_append`` with the offset
 read on the device); ``compute`` draws the subsets' row indices on the device and evaluates every subset in ONE call of
 ``otvae_poly_mmd_subsets`` (csrc/kid.hip): fp64 on the matrix cores, rows gathered at the load, fixed summation order."""
-import warnings
-from typing import Any, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
-from .base import Metric
-from .features import ImageFeatureMixin
+from .features import FeatureStore, ImageFeatureMixin
 
 __all__ = ["poly_mmd2", "kernel_distance", "KernelDistance", "KernelInceptionDistance"]
 
@@ -115,11 +113,11 @@ def kernel_distance(real: Tensor, fake: Tensor, subsets: int = 100, subset_size:
     return stats[0], stats[1]
 
 
-class KernelDistance(Metric):
+class KernelDistance(FeatureStore):
     """The metric on features the caller already has: ``update(generated_feats, sample_feats)``, each ``[B, feature_size]`` (more
-    dimensions are flattened), float32 or float64 (ROUNDED to float32 when stored), either may be None -- the keyword names and their
-    pairing are ``FrechetDistance``'s (``generated`` feeds the ``real_*`` states, ``samples`` the ``fake_*`` ones; the distance is
-    symmetric).  Per side the states are ``*_features`` ``[max_observations, feature_size]`` float32 and ``num_*`` int64 ``[2]`` =
+    dimensions are flattened), float32 or float64 (ROUNDED to float32 when stored), either may be None; the store itself is
+    ``features.FeatureStore``.  The keyword names and their pairing are ``FrechetDistance``'s (``generated`` feeds the ``real_*``
+    states, ``samples`` the ``fake_*`` ones; the distance is symmetric).  Per side the states are ``*_features`` ``[max_observations, feature_size]`` float32 and ``num_*`` int64 ``[2]`` =
     (rows stored, rows seen); rows beyond ``max_observations`` are dropped (``compute`` warns once).  ``update`` is one
     ``otvae::feature_append`` per side and reads nothing on the host, so it can be captured.
 
@@ -129,6 +127,7 @@ class KernelDistance(Metric):
     per_subset)`` keeps what the last call used.  Host-resident states (gathered or pre-filled) take an fp64 torch path."""
     higher_is_better = False
     compute_names = ("mean", "std")
+    _store_name = "KernelDistance"
 
     def __init__(self, feature_size: int = 2048, max_observations: int = 10000, subsets: int = 100, subset_size: int = 1000,
                  degree: int = 3, gamma: Optional[float] = None, coef: float = 1.0, seed: Optional[int] = None, **metric_kwargs):
@@ -143,27 +142,7 @@ class KernelDistance(Metric):
         self.subsets, self.subset_size, self.seed = subsets, subset_size, seed
         self.last_subsets: Optional[Tuple[Tensor, Tensor, Tensor]] = None
         self._compute_calls = 0
-        self._warned_dropped = False
-        for side in ("real", "fake"):
-            self.add_state(f"{side}_features", torch.zeros(max_observations, feature_size, dtype=torch.float32), dist_reduce_fx="sum")
-            self.add_state(f"num_{side}", torch.zeros(2, dtype=torch.int64), dist_reduce_fx="sum")
-
-    def reset(self) -> None:
-        """the counts go to zero in place; the feature buffers keep their contents (rows beyond the count are never read) and, after a
-        ``sync`` enlarged them, return to their own size"""
-        for side in ("real", "fake"):
-            getattr(self, f"num_{side}").zero_()
-            buf = getattr(self, f"{side}_features")
-            if buf.shape[0] != self.max_observations:
-                setattr(self, f"{side}_features", buf[:self.max_observations].clone())
-
-    def _append(self, feats: Tensor, side: str) -> None:
-        feats = feats.detach().reshape(feats.shape[0], -1)
-        if feats.shape[1] != self.feature_size:
-            raise ValueError(f"features have width {feats.shape[1]}, the metric was built for {self.feature_size}")
-        if feats.dtype not in (torch.float32, torch.float64):
-            feats = feats.float()
-        torch.ops.otvae.feature_append(feats, getattr(self, f"{side}_features"), getattr(self, f"num_{side}"))
+        self._init_store(feature_size, max_observations)
 
     def update(self, generated: Optional[Tensor] = None, samples: Optional[Tensor] = None) -> None:
         if generated is not None:
@@ -172,13 +151,11 @@ class KernelDistance(Metric):
             self._append(samples, "fake")
 
     def compute(self) -> Tuple[Tensor, Tensor]:
-        (stored_real, seen_real), (stored_fake, seen_fake) = self.num_real.tolist(), self.num_fake.tolist()
+        counts = self._read_counts()
+        stored_real, stored_fake = counts[0][0], counts[1][0]
         if min(stored_real, stored_fake) < self.subset_size:
             raise ValueError(_SUBSET_SIZE_ERROR)
-        if (seen_real > stored_real or seen_fake > stored_fake) and not self._warned_dropped:
-            self._warned_dropped = True
-            warnings.warn(f"KernelDistance keeps the first max_observations = {self.max_observations} feature rows per side: "
-                          f"{seen_real - stored_real} real and {seen_fake - stored_fake} fake rows were dropped", UserWarning)
+        self._warn_dropped(counts)
         device = self.real_features.device
         g = _generator(device, self.seed, self._compute_calls)
         self._compute_calls += 1
@@ -188,32 +165,6 @@ class KernelDistance(Metric):
                                self.degree, self.gamma, self.coef)
         self.last_subsets = (idx_real, idx_fake, per)
         return stats[0], stats[1]
-
-    def sync(self, process_group: Any = None) -> None:
-        """the union of every rank's stored rows, rank 0's first, in the front of buffers of ``world x max_observations`` rows (the
-        fixed-size buffers and the counts are all-gathered: features cannot be sum-reduced); nothing to do without a process group"""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()):
-            return
-        group = process_group if process_group is not None else self.process_group
-        world = dist.get_world_size(group)
-        if world == 1:
-            return
-        for side in ("real", "fake"):
-            buf, num = getattr(self, f"{side}_features"), getattr(self, f"num_{side}")
-            rows = buf.shape[0]
-            nums = [torch.empty_like(num) for _ in range(world)]
-            bufs = [torch.empty_like(buf) for _ in range(world)]
-            dist.all_gather(nums, num.contiguous(), group=group)
-            dist.all_gather(bufs, buf.contiguous(), group=group)
-            counts = torch.stack(nums).tolist()
-            merged = buf.new_zeros(world * rows, buf.shape[1])
-            at = 0
-            for (stored, _), part in zip(counts, bufs):
-                merged[at:at + stored] = part[:stored]
-                at += stored
-            setattr(self, f"{side}_features", merged)
-            num.copy_(torch.tensor([at, sum(seen for _, seen in counts)], dtype=num.dtype))
 
 
 class KernelInceptionDistance(ImageFeatureMixin, KernelDistance):

@@ -26,6 +26,9 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
     otvae::feature_append           KernelInceptionDistance.update's store      torchmetrics' kid       (in place, no gradient)
     otvae::poly_mmd_subsets         KernelInceptionDistance.compute: the MMD^2   torchmetrics' kid       (no gradient)
                                     of every random subset and their mean / std
+    otvae::knn_sq_radii             PrecisionRecall.compute: k-NN ball radii     no reference class      (no gradient)
+    otvae::manifold_counts          PrecisionRecall.compute: ball memberships    no reference class      (no gradient)
+                                    and nearest-sample distances
 
 The modules call these through ``functional`` (``qkv_attention``, ``gaussian_prior``, ``nelbo_loss``, the OT priors,
 ``soft_cross_entropy``, ``gaussian_blur``).
@@ -889,6 +892,64 @@ def _feature_append(feats: Tensor, buf: Tensor, count: Tensor) -> None:
 _define("poly_mmd_subsets", "(Tensor real, Tensor fake, Tensor? idx_real, Tensor? idx_fake, int subset_size, int degree, float gamma, "
         "float coef) -> (Tensor per_subset, Tensor stats)", _poly_mmd_subsets, _poly_mmd_subsets_fake)
 _define("feature_append", "(Tensor feats, Tensor(a!) buf, Tensor(b!) count) -> ()", _feature_append, lambda feats, buf, count: None)
+
+
+# ------------------------------------------------------------------------------------------------ k-NN manifold statistics
+def _manifold_features(op: str, name: str, t: Tensor) -> None:
+    _lib.require_cuda(t, f"{name} features")
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be a contiguous [n, D] float32 tensor, got {tuple(t.shape)} {t.dtype}")
+
+
+def _knn_sq_radii(x: Tensor, k: int) -> Tensor:
+    """``r2 [n]`` float64: the k-th smallest squared distance from each row to the OTHER rows (self excluded by index)"""
+    lib = _lib.load()
+    _manifold_features("knn_sq_radii", "x", x)
+    n, d = x.shape
+    nbytes = lib.otvae_knn_sq_radii_ws(n, d, int(k))
+    if nbytes < 0:
+        raise ValueError(f"knn_sq_radii: need 1 <= k <= 16, k < n <= 2^21 rows and a feature width in 1 ... 2048, got k = {k}, "
+                         f"x {tuple(x.shape)}")
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    r2 = torch.empty(n, device=x.device, dtype=torch.float64)
+    check(lib.otvae_knn_sq_radii(ptr(x), n, d, int(k), ptr(r2), ptr(ws), stream()), "otvae_knn_sq_radii")
+    return r2
+
+
+def _manifold_counts(real: Tensor, r2_real: Tensor, fake: Tensor, r2_fake: Tensor):
+    """``(count_fake [M] int32, hit_real [N] int32, min_real [N] float64)`` of ``otvae_manifold_counts``"""
+    lib = _lib.load()
+    _manifold_features("manifold_counts", "real", real)
+    _manifold_features("manifold_counts", "fake", fake)
+    if real.shape[1] != fake.shape[1]:
+        raise ValueError(f"manifold_counts: feature widths differ ({real.shape[1]} and {fake.shape[1]})")
+    for name, r, f in (("r2_real", r2_real, real), ("r2_fake", r2_fake, fake)):
+        _lib.require_cuda(r, name)
+        if r.dtype != torch.float64 or tuple(r.shape) != (f.shape[0],) or not r.is_contiguous():
+            raise ValueError(f"manifold_counts: {name} must be a contiguous float64 tensor of shape ({f.shape[0]},), got "
+                             f"{tuple(r.shape)} {r.dtype}")
+    (n, d), m = real.shape, fake.shape[0]
+    nbytes = lib.otvae_manifold_counts_ws(n, m, d)
+    if nbytes < 0:
+        raise ValueError(f"manifold_counts: need 2 <= rows <= 2^21 per side and a feature width in 1 ... 2048, got real "
+                         f"{tuple(real.shape)}, fake {tuple(fake.shape)}")
+    ws = torch.empty(nbytes, device=real.device, dtype=torch.uint8)
+    count_fake = torch.empty(m, device=real.device, dtype=torch.int32)
+    hit_real = torch.empty(n, device=real.device, dtype=torch.int32)
+    min_real = torch.empty(n, device=real.device, dtype=torch.float64)
+    check(lib.otvae_manifold_counts(ptr(real), ptr(r2_real), n, ptr(fake), ptr(r2_fake), m, d, ptr(count_fake), ptr(hit_real),
+                                    ptr(min_real), ptr(ws), stream()), "otvae_manifold_counts")
+    return count_fake, hit_real, min_real
+
+
+def _manifold_counts_fake(real, r2_real, fake, r2_fake):
+    return (fake.new_empty((fake.shape[0],), dtype=torch.int32), real.new_empty((real.shape[0],), dtype=torch.int32),
+            real.new_empty((real.shape[0],), dtype=torch.float64))
+
+
+_define("knn_sq_radii", "(Tensor x, int k) -> Tensor", _knn_sq_radii, lambda x, k: x.new_empty((x.shape[0],), dtype=torch.float64))
+_define("manifold_counts", "(Tensor real, Tensor r2_real, Tensor fake, Tensor r2_fake) -> (Tensor count_fake, Tensor hit_real, "
+        "Tensor min_real)", _manifold_counts, _manifold_counts_fake)
 
 SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP, SSIM_RANGE_BATCH = 0, 1, 2   # otvae_ssim_accum's range_mode
 
