@@ -782,7 +782,9 @@ int otvae_apply_transport(int dtype, const void* x, const double* ms, const doub
                           int nb, int B, int D, void* y, void* stream);
 
 /* ---- CodebookModel.energy/assign 'argmax'/predict (ot/distribution_models/codebook_model.py:150-160,
- *      base.py:216-233): x[nb][B][d], codebook[nb][K][d] -> idx[nb][B] (int64), enc[nb][B][d] = codebook[idx] */
+ *      base.py:216-233): x[nb][B][d], codebook[nb][K][d] -> idx[nb][B] (int64), enc[nb][B][d] = codebook[idx].
+ *      idx is always in [0, K): a sample with a NaN weight (NaN component, or any NaN atom) gets 0, the reference's
+ *      argmax(softmax(.)) of a row that the NaN has made all NaN. */
 int otvae_codebook_assign(const float* x, const float* codebook, int nb, int B, int K, int d, float temperature,
                           int64_t* idx, float* enc, void* stream);
 /* The assignment distribution itself (base.py:216-224): probs[nb][B][K] = softmax_k(energy/temperature), and

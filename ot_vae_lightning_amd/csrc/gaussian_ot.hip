@@ -1186,6 +1186,7 @@ __global__ __launch_bounds__(256) void codebook_assign_kernel(const float* __res
     const float* cbb = cb + (size_t)b * K * d;
     float best = -INFINITY;
     int besti = 0x7fffffff;
+    bool has_nan = false;
     for (int k = lane; k < K; k += 64) {
         float s = 0.f;
         for (int j = 0; j < d; ++j) {
@@ -1193,6 +1194,7 @@ __global__ __launch_bounds__(256) void codebook_assign_kernel(const float* __res
             s = fmaf(t, t, s);
         }
         const float e = (1.f / (sqrtf(s) + 1e-8f)) * inv_temp;
+        has_nan |= e != e;
         if (e > best) {
             best = e;
             besti = k;
@@ -1207,6 +1209,10 @@ __global__ __launch_bounds__(256) void codebook_assign_kernel(const float* __res
             besti = oi;
         }
     }
+    // a NaN weight (NaN latent or atom) makes the reference's whole softmax row NaN, and torch.argmax of that is 0; a row of NaN
+    // only would otherwise leave besti at its start value, far outside the codebook.  Every other weight is >= 0, so k = 0 beats
+    // the start value and besti < K.
+    if (__any(has_nan)) besti = 0;
     if (lane == 0) idx[(size_t)b * B + r] = besti;
     for (int j = lane; j < d; j += 64) enc[((size_t)b * B + r) * d + j] = cbb[(size_t)besti * d + j];
 }
