@@ -496,14 +496,31 @@ int otvae_normal_fill(float* out, int64_t n, int64_t* key, int stream_id, int ad
 /* a[nb][N], b[nb][M], C[nb][N][M] -> pi[nb][N][M] (may alias no input), u[nb][N], v[nb][M] potentials.
  * dtype: 0 = fp32, 1 = fp64.  ws: bytes from otvae_sinkhorn_ws.  Stops all problems at the first iteration where
  * min over the batch of (|du|_1+|dv|_1) < threshold, evaluated on the device (no host sync); threshold <= 0
- * runs exactly max_iter iterations.  iters_done (device int32, may be NULL). */
+ * runs exactly max_iter iterations.  iters_done (device int32, may be NULL).
+ * Every route below gives the same bits.  otvae_sinkhorn_route tells which one a problem takes, from its shape alone (it neither
+ * queries the device nor reads the environment; `tracked` = threshold > 0; -1 for a bad argument):
+ *   OTVAE_SK_ROUTE_LAUNCHES (0)      one launch per half-iteration: N or M > 1024, more than 4096 (fp32) / 1024 (fp64) rows, where
+ *                                    rows = nb * max(N, M); also every problem when OTVAE_SK_MULTILAUNCH is set in the environment
+ *   OTVAE_SK_ROUTE_BARRIER | rpw     all iterations in one launch of cdiv(rows, 8 rpw) <= 128 workgroups of 512 threads, a wave keeping
+ *                                    rpw rows of each matrix in registers (1 up to 1024 rows, 2 up to 2048, 4 up to 4096), the
+ *                                    potentials exchanged through a counter barrier: fp64, and fp32 when tracked
+ *   OTVAE_SK_ROUTE_FLAGS | rpw       the same with every potential entry travelling as one {epoch, value} word and no barrier:
+ *                                    fp32 with a fixed iteration count
+ * The workgroups of a one-launch solve wait for each other, so the solve checks at run time that the device holds them all at
+ * once and takes the launches if not.  That guard cannot bind here for the shapes above: they need at most 128 workgroups, the
+ * MI355X has 256 CUs, and every CU holds at least one 512-thread workgroup of these kernels (their launch bound keeps the registers
+ * within one CU's file, and the potential takes <= 16 KiB of LDS). */
+#define OTVAE_SK_ROUTE_LAUNCHES 0
+#define OTVAE_SK_ROUTE_BARRIER 0x10
+#define OTVAE_SK_ROUTE_FLAGS 0x20
+int otvae_sinkhorn_route(int dtype, int nb, int N, int M, int tracked);
 int64_t otvae_sinkhorn_ws(int dtype, int nb, int N, int M);
 int otvae_sinkhorn_log(int dtype, const void* a, const void* b, const void* C, int nb, int N, int M,
                        double reg, int max_iter, double threshold, void* ws,
                        void* pi, void* u, void* v, int32_t* iters_done, void* stream);
 /* The reference's sinkhorn_log is plain torch arithmetic: autograd differentiates it through every iteration with respect to
  * a, b and C (ot/w2_utils.py:301-319).  These two entry points are that derivative.  otvae_sinkhorn_log_tape: the same solve (one
- * launch per half-iteration, identical arithmetic and stopping rule) that also keeps what the reverse sweep needs in `tape`
+ * launch per half-iteration, the kernels of otvae_sinkhorn_log's launch route: identical bits and stopping rule) that also keeps what the reverse sweep needs in `tape`
  * (otvae_sinkhorn_tape_bytes: Cr, Cr^T, log marginals, the potentials of every iteration, the iteration count).
  * otvae_sinkhorn_log_bwd: gpi[nb][N][M] = dL/dpi -> gC[nb][N][M], ga[nb][N], gb[nb][M] (each may be NULL; ga / gb need a / b),
  * ws: otvae_sinkhorn_bwd_ws bytes.  The iteration count the forward stopped at is read on the device (no host sync). */

@@ -8,158 +8,13 @@
 // with wave shuffles.  The column pass runs on a transposed copy of Cr made once, so both passes read contiguous
 // rows; for the benchmark size (1024x1024 fp32) both copies stay L2/MALL resident across the 100 passes.
 // The reference's per-iteration host sync (.item()) becomes a device flag tested at the top of every kernel.
-#include "common.h"
+// Eligible shapes (sk_route below) run all iterations in one launch instead, rows in registers; OTVAE_SK_MULTILAUNCH=1 keeps
+// every shape on the launches.  The arithmetic of the iteration (initialisation, row log-sum-exp in both forms, stopping test,
+// plan row) is in sinkhorn_rows.h, shared with the tape-recording forward of sinkhorn_diff.hip.
+#include <type_traits>
+#include "sinkhorn_rows.h"
 
-template <typename T>
-struct MathT;
-template <>
-struct MathT<float> {
-    static __device__ __forceinline__ float exp(float x) { return __expf(x); }
-    static __device__ __forceinline__ float log(float x) { return __logf(x); }
-    static __device__ __forceinline__ float ninf() { return -INFINITY; }
-};
-template <>
-struct MathT<double> {
-    static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
-    static __device__ __forceinline__ double log(double x) { return ::log(x); }
-    static __device__ __forceinline__ double ninf() { return -(double)INFINITY; }
-};
-
-struct SkCtl {
-    int done;            // set by sk_check when the batch-min difference drops below the threshold
-    int iters;           // iterations actually performed
-    unsigned bar_count;  // persistent kernel: monotone arrival counter of the grid barrier
-    int timeout;         // persistent kernel: a wait ran out (the plan, the potentials and the cost are poisoned with NaN; iters = -1)
-    unsigned spin_limit; // persistent kernel: polls a wait may spend before it gives up (OTVAE_SK_SPIN_LIMIT, default 2^22)
-};
-
-// Cr = -C/(reg * cmax) (row major, into `cr`) and its transpose (into `crt`), 32x32 tiles through LDS.  cmax = the
-// maximum of problem b's cost matrix, reduced here from the P partial maxima its producer left (otvae_sqdist's epilogue),
-// or 1 when pmax == NULL: the `cost_matrix / max_per_mat` of batch_ot_gmm (ot/w2_utils.py:265-266) without a pass of its
-// own.  The blocks of the first tile row / column also initialise the potentials and the log-marginals (a, b == NULL:
-// uniform 1/N, 1/M), block (0,0,0) the control block.
-template <typename T>
-__global__ __launch_bounds__(256) void sk_init_mat(const T* __restrict__ Cm, int N, int M, T inv_reg, const T* __restrict__ pmax, int P,
-                                                   T* __restrict__ cr, T* __restrict__ crt, const T* __restrict__ a,
-                                                   const T* __restrict__ b, T* __restrict__ loga, T* __restrict__ logb,
-                                                   T* __restrict__ u, T* __restrict__ v, SkCtl* ctl, int preset_iters,
-                                                   unsigned spin_limit, unsigned long long* __restrict__ tu,
-                                                   unsigned long long* __restrict__ tv, T* __restrict__ scale_out) {
-    __shared__ T tile[32][33];
-    __shared__ T s_red[4];
-    const int pb = blockIdx.z;
-    const size_t boff = (size_t)pb * N * M;
-    const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    T neg_scale = -inv_reg;
-    if (pmax) {
-        T mx = MathT<T>::ninf();
-        for (int i = threadIdx.x; i < P; i += 256) {
-            const T q = pmax[(size_t)pb * P + i];
-            mx = q > mx ? q : mx;
-        }
-        mx = wave_max(mx);
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = mx;
-        __syncthreads();
-        const T m01 = s_red[0] > s_red[1] ? s_red[0] : s_red[1], m23 = s_red[2] > s_red[3] ? s_red[2] : s_red[3];
-        const T cmax = m01 > m23 ? m01 : m23;
-        neg_scale = -inv_reg / cmax;
-        if (scale_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) scale_out[pb] = cmax;
-    }
-    for (int r = ty; r < 32; r += 8) {
-        const int i = i0 + r, j = j0 + tx;
-        if (i < N && j < M) {
-            const T val = Cm[boff + (size_t)i * M + j] * neg_scale;
-            cr[boff + (size_t)i * M + j] = val;
-            tile[r][tx] = val;
-        }
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const int j = j0 + r, i = i0 + tx;
-        if (i < N && j < M) crt[boff + (size_t)j * N + i] = tile[tx][r];
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 32 && i0 + (int)threadIdx.x < N) {
-        const size_t i = (size_t)pb * N + i0 + threadIdx.x;
-        loga[i] = MathT<T>::log((a ? a[i] : (T)1 / (T)N) + (T)1e-8);
-        u[i] = (T)0;
-        if (tu) tu[i] = 0ull;  // {epoch 0, +0.0f}: the tagged potentials of sk_persistent_tagged
-    }
-    if (blockIdx.y == 0 && threadIdx.x >= 64 && threadIdx.x < 96 && j0 + (int)threadIdx.x - 64 < M) {
-        const size_t j = (size_t)pb * M + j0 + threadIdx.x - 64;
-        logb[j] = MathT<T>::log((b ? b[j] : (T)1 / (T)M) + (T)1e-8);
-        v[j] = (T)0;
-        if (tv) tv[j] = 0ull;
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 128) {
-        ctl->done = 0;
-        ctl->iters = preset_iters;
-        ctl->bar_count = 0;
-        ctl->timeout = 0;
-        ctl->spin_limit = spin_limit;
-    }
-}
-
-// out[r] = logm[r] - LSE_l(mat[r][l] + add[l]);  absd[r] = |out_new - out_old|.  One wave per row.
-template <typename T>
-__global__ __launch_bounds__(256) void sk_pass(const T* __restrict__ mat, const T* __restrict__ add, const T* __restrict__ logm,
-                                               int R, int L, T* __restrict__ out, T* __restrict__ absd, const SkCtl* ctl) {
-    if (ctl->done) return;
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const int b = blockIdx.y;
-    const T* row = mat + ((size_t)b * R + r) * L;
-    const T* ad = add + (size_t)b * L;
-    T mx = MathT<T>::ninf();
-    for (int l = lane; l < L; l += 64) {
-        const T x = row[l] + ad[l];
-        mx = x > mx ? x : mx;
-    }
-    mx = wave_max(mx);
-    T s = (T)0;
-    for (int l = lane; l < L; l += 64) s += MathT<T>::exp(row[l] + ad[l] - mx);
-    s = wave_sum(s);
-    if (lane == 0) {
-        const T nv = logm[(size_t)b * R + r] - (mx + MathT<T>::log(s));
-        const T old = out[(size_t)b * R + r];
-        out[(size_t)b * R + r] = nv;
-        if (absd) {
-            const T d = nv - old;
-            absd[(size_t)b * R + r] = d < (T)0 ? -d : d;
-        }
-    }
-}
-
-// one block: diff_b = sum |du| + sum |dv| per problem, done = (min_b diff_b < threshold); counts the iteration
-template <typename T>
-__global__ __launch_bounds__(256) void sk_check(const T* __restrict__ adu, const T* __restrict__ adv, int nb, int N, int M,
-                                                double threshold, SkCtl* ctl) {
-    __shared__ double red[4];
-    __shared__ double best;
-    if (ctl->done) return;
-    if (threadIdx.x == 0) best = INFINITY;
-    __syncthreads();
-    for (int b = 0; b < nb; ++b) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < N; i += 256) s += (double)adu[(size_t)b * N + i];
-        for (int i = threadIdx.x; i < M; i += 256) s += (double)adv[(size_t)b * M + i];
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            // the reference sums in the tensor dtype; compare in that dtype
-            const T d = (T)((red[0] + red[1]) + (red[2] + red[3]));
-            if ((double)d < best) best = (double)d;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ctl->iters += 1;
-        if (best < threshold) ctl->done = 1;
-    }
-}
-
+// pi = exp(u_i + v_j + Cr_ij) in place over Cr, after the launches
 template <typename T>
 __global__ __launch_bounds__(256) void sk_pi(T* __restrict__ pi_cr, const T* __restrict__ u, const T* __restrict__ v, int N,
                                              int M) {
@@ -175,8 +30,8 @@ __global__ __launch_bounds__(256) void sk_pi(T* __restrict__ pi_cr, const T* __r
 // ------------------------------------------------------------------------------------------------ persistent solver
 // All iterations in ONE launch.  A half-iteration needs every entry of the other potential, i.e. a grid-wide exchange;
 // with one launch per half-iteration the 100 passes of the 50-iteration solve cost ~100 launch ramps (5-9 us each) for
-// ~1 us of arithmetic.  Here <= one workgroup per CU stays resident, a wave owns one row of Cr and one row of Cr^T and
-// (when they are <= 1024 long and there are enough waves) keeps both IN REGISTERS for the whole solve, so that per
+// ~1 us of arithmetic.  Here <= one workgroup per CU stays resident, a wave owns up to 4 rows of Cr and of Cr^T (<= 1024
+// long) and keeps them IN REGISTERS for the whole solve, so that per
 // half-iteration only the 4 KiB potential crosses the chip: written with agent-scope (sc1, write-through) stores,
 // published by a monotone arrival counter, read with agent-scope loads (cdna_hip_programming.md section 6 Guideline 16,
 // sc1 form).  Every wait is bounded; the arithmetic per row is the one of sk_pass, so both paths give identical bits.
@@ -233,89 +88,39 @@ __device__ __forceinline__ bool sk_grid_barrier(SkCtl* ctl, unsigned nblocks, un
     return s_ok != 0;
 }
 
-#define SK_EPL 16  // row elements per lane that may live in registers (rows up to 1024)
-
-// NTH threads per workgroup (NTH / 64 waves), every wave owns RPW rows of Cr and RPW rows of Cr^T (rows wave_g + q * nwaves)
-// and, with CACHE, keeps them in registers for the whole solve.  POTLDS: the potential of the other side is fetched ONCE per
-// workgroup and half-iteration (one coherent load per thread) into LDS instead of 16 coherent loads per lane and row.
-// Few large workgroups (32 x 1024 threads for a 1024 x 1024 problem) keep the barrier cheap: its cost is the serialised
+// 512 threads per workgroup (8 waves), every wave owns RPW rows of Cr and RPW rows of Cr^T (rows wave_g + q * nwaves) and keeps
+// them in registers for the whole solve.  The potential of the other side is fetched ONCE per workgroup and half-iteration
+// (one coherent load per thread) into LDS.  Few large workgroups (<= 128) keep the barrier cheap: its cost is the serialised
 // arrivals on one counter plus one round trip, and it was ~10 us with 256 workgroups.
-template <typename T, bool CACHE, int RPW, int NTH, bool POTLDS>
-__global__ __launch_bounds__(NTH) void sk_persistent(T* __restrict__ pi_cr, const T* __restrict__ crt, const T* __restrict__ loga,
+template <typename T, int RPW>
+__global__ __launch_bounds__(512) void sk_persistent(T* __restrict__ pi_cr, const T* __restrict__ crt, const T* __restrict__ loga,
                                                      const T* __restrict__ logb, T* __restrict__ u, T* __restrict__ v,
                                                      T* __restrict__ adu, T* __restrict__ adv, int nb, int N, int M, int max_iter,
                                                      double threshold, SkCtl* ctl) {
     extern __shared__ __align__(16) char sk_smem[];
-    T* pot = reinterpret_cast<T*>(sk_smem);  // POTLDS: nb * max(N, M) entries
-    __shared__ double red[4];
-    __shared__ double s_best;
-    constexpr int WPB = NTH / 64;
+    T* pot = reinterpret_cast<T*>(sk_smem);  // nb * max(N, M) entries
     const int lane = threadIdx.x & 63;
-    const int wave_g = blockIdx.x * WPB + (threadIdx.x >> 6), nwaves = gridDim.x * WPB;
+    const int wave_g = blockIdx.x * 8 + (threadIdx.x >> 6), nwaves = gridDim.x * 8;
     const bool track = threshold > 0.0;
     unsigned epoch = 0;
     const int RU = nb * N, RV = nb * M;  // rows of the u pass (rows of Cr) / of the v pass (rows of Cr^T)
+    T cr_row[RPW][SK_EPL], ct_row[RPW][SK_EPL];
+    sk_reg_rows_load(cr_row, pi_cr, RU, M, wave_g, nwaves, lane);
+    sk_reg_rows_load(ct_row, crt, RV, N, wave_g, nwaves, lane);
 
-    // register-resident rows (CACHE: RPW rows of each matrix per wave at most)
-    constexpr int NC = CACHE ? RPW : 1, EC = CACHE ? SK_EPL : 1;
-    T cr_row[NC][EC], ct_row[NC][EC];
-    if constexpr (CACHE) {
+    // one pass: out[r] = logm[r] - LSE_l(row[l] + add[l]) with the potential `add` read coherently
+    auto row_pass = [&](const T (&cached)[RPW][SK_EPL], const T* __restrict__ add, const T* __restrict__ logm, int R, int L,
+                        int rows_per_problem, T* __restrict__ out, T* __restrict__ absd) {
+        __syncthreads();  // the previous pass's readers are done with pot
+        for (int i = threadIdx.x; i < nb * L; i += 512) pot[i] = CohT<T>::ld(add + i);
+        __syncthreads();
 #pragma unroll
         for (int q = 0; q < RPW; ++q) {
             const int r = wave_g + q * nwaves;
-#pragma unroll
-            for (int k = 0; k < SK_EPL; ++k) {
-                const int l = lane + 64 * k;
-                cr_row[q][k] = (r < RU && l < M) ? pi_cr[(size_t)r * M + l] : MathT<T>::ninf();
-                ct_row[q][k] = (r < RV && l < N) ? crt[(size_t)r * N + l] : MathT<T>::ninf();
-            }
-        }
-    }
-
-    // one pass: out[r] = logm[r] - LSE_l(row[l] + add[l]) with the potential `add` read coherently
-    auto row_pass = [&](const T* __restrict__ mat, const T (&cached)[NC][EC], const T* __restrict__ add,
-                        const T* __restrict__ logm, int R, int L, int rows_per_problem, T* __restrict__ out, T* __restrict__ absd) {
-        if constexpr (POTLDS) {
-            __syncthreads();  // the previous pass's readers are done with pot
-            for (int i = threadIdx.x; i < nb * L; i += NTH) pot[i] = CohT<T>::ld(add + i);
-            __syncthreads();
-        }
-        int q = 0;
-        for (int r = wave_g; r < R; r += nwaves, ++q) {
-            const int b = r / rows_per_problem;
-            const T* ad = add + (size_t)b * L;
-            const T* pl = pot + (size_t)b * L;
-            auto potential = [&](int l) -> T { return POTLDS ? pl[l] : CohT<T>::ld(ad + l); };
-            T mx = MathT<T>::ninf();
-            T s = (T)0;
-            if constexpr (CACHE) {
-                T x[SK_EPL];
-#pragma unroll
-                for (int qq = 0; qq < RPW; ++qq) {  // q is wave-uniform: a compile-time index into the register rows
-                    if (qq != q) continue;
-#pragma unroll
-                    for (int k = 0; k < SK_EPL; ++k) {
-                        const int l = lane + 64 * k;
-                        x[k] = l < L ? cached[qq][k] + potential(l) : MathT<T>::ninf();
-                        mx = x[k] > mx ? x[k] : mx;
-                    }
-                }
-                mx = wave_max(mx);
-#pragma unroll
-                for (int k = 0; k < SK_EPL; ++k)
-                    if (lane + 64 * k < L) s += MathT<T>::exp(x[k] - mx);
-            } else {
-                const T* row = mat + (size_t)r * L;
-                for (int l = lane; l < L; l += 64) {
-                    const T x = row[l] + potential(l);
-                    mx = x > mx ? x : mx;
-                }
-                mx = wave_max(mx);
-                for (int l = lane; l < L; l += 64) s += MathT<T>::exp(row[l] + potential(l) - mx);
-            }
-            s = wave_sum(s);
+            if (r >= R) continue;
+            const T lse = sk_reg_row_lse(cached[q], pot + (size_t)(r / rows_per_problem) * L, L, lane);
             if (lane == 0) {
-                const T nv = logm[r] - (mx + MathT<T>::log(s));
+                const T nv = logm[r] - lse;
                 if (absd) {
                     const T d = nv - CohT<T>::ld(out + r);
                     CohT<T>::st(absd + r, d < (T)0 ? -d : d);
@@ -328,33 +133,16 @@ __global__ __launch_bounds__(NTH) void sk_persistent(T* __restrict__ pi_cr, cons
     int it = 0;
     bool alive = true;
     for (; it < max_iter && alive; ++it) {
-        row_pass(crt, ct_row, u, logb, RV, N, M, v, track ? adv : nullptr);
+        row_pass(ct_row, u, logb, RV, N, M, v, track ? adv : nullptr);
         alive = sk_grid_barrier(ctl, gridDim.x, epoch);
         if (!alive) break;
-        row_pass(pi_cr, cr_row, v, loga, RU, M, N, u, track ? adu : nullptr);
+        row_pass(cr_row, v, loga, RU, M, N, u, track ? adu : nullptr);
         alive = sk_grid_barrier(ctl, gridDim.x, epoch);
         if (!alive) break;
         if (track) {
-            // every block evaluates the same test on the same numbers in the same order: a uniform decision without
-            // another exchange (sk_check's arithmetic: 256 threads, 4 waves, whatever the workgroup size)
-            if (threadIdx.x == 0) s_best = INFINITY;
-            __syncthreads();
-            for (int b = 0; b < nb; ++b) {
-                if (threadIdx.x < 256) {
-                    double s = 0.0;
-                    for (int i = threadIdx.x; i < N; i += 256) s += (double)CohT<T>::ld(adu + (size_t)b * N + i);
-                    for (int i = threadIdx.x; i < M; i += 256) s += (double)CohT<T>::ld(adv + (size_t)b * M + i);
-                    s = wave_sum(s);
-                    if (lane == 0) red[threadIdx.x >> 6] = s;
-                }
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    const T d = (T)((red[0] + red[1]) + (red[2] + red[3]));
-                    if ((double)d < s_best) s_best = (double)d;
-                }
-                __syncthreads();
-            }
-            const bool stop = s_best < threshold;
+            // every block evaluates sk_check's test on the same numbers in the same order: a uniform decision without
+            // another exchange
+            const bool stop = sk_min_diff<T>(adu, adv, nb, N, M, [](const T* p) { return CohT<T>::ld(p); }) < threshold;
             if (blockIdx.x == 0 && threadIdx.x == 0) ctl->iters = it + 1;
             __syncthreads();
             if (stop) {
@@ -368,25 +156,12 @@ __global__ __launch_bounds__(NTH) void sk_persistent(T* __restrict__ pi_cr, cons
         return;
     }
     // pi = exp(u_i + v_j + Cr_ij), rows of Cr
-    int q = 0;
-    for (int r = wave_g; r < RU; r += nwaves, ++q) {
-        const int b = r / N;
-        const T ui = CohT<T>::ld(u + r);
-        const T* vb = v + (size_t)b * M;
-        T* row = pi_cr + (size_t)r * M;
-        if constexpr (CACHE) {
 #pragma unroll
-            for (int qq = 0; qq < RPW; ++qq) {
-                if (qq != q) continue;
-#pragma unroll
-                for (int k = 0; k < SK_EPL; ++k) {
-                    const int l = lane + 64 * k;
-                    if (l < M) row[l] = MathT<T>::exp(ui + CohT<T>::ld(vb + l) + cr_row[qq][k]);
-                }
-            }
-        } else {
-            for (int l = lane; l < M; l += 64) row[l] = MathT<T>::exp(ui + CohT<T>::ld(vb + l) + row[l]);
-        }
+    for (int q = 0; q < RPW; ++q) {
+        const int r = wave_g + q * nwaves;
+        if (r >= RU) continue;
+        const T* vb = v + (size_t)(r / N) * M;
+        sk_reg_row_plan(pi_cr + (size_t)r * M, cr_row[q], CohT<T>::ld(u + r), M, lane, [&](int l) { return CohT<T>::ld(vb + l); });
     }
 }
 
@@ -397,8 +172,8 @@ __global__ __launch_bounds__(NTH) void sk_persistent(T* __restrict__ pi_cr, cons
 // after it has read every entry of the OTHER potential at epoch p, which every workgroup writes only after reading the
 // first one at epoch p-1: the data dependence itself keeps a word from being overwritten before all its readers have
 // it.  Every poll is bounded (SK_SPIN_LIMIT); the arithmetic per row is sk_pass's.
-template <int RPW, int NTH>
-__global__ __launch_bounds__(NTH) void sk_persistent_tagged(float* __restrict__ pi_cr, const float* __restrict__ crt,
+template <int RPW>
+__global__ __launch_bounds__(512) void sk_persistent_tagged(float* __restrict__ pi_cr, const float* __restrict__ crt,
                                                             const float* __restrict__ loga, const float* __restrict__ logb,
                                                             float* __restrict__ u, float* __restrict__ v,
                                                             unsigned long long* __restrict__ tu, unsigned long long* __restrict__ tv,
@@ -406,21 +181,13 @@ __global__ __launch_bounds__(NTH) void sk_persistent_tagged(float* __restrict__ 
     extern __shared__ __align__(16) char sk_smem[];
     float* pot = reinterpret_cast<float*>(sk_smem);
     __shared__ int s_fail;
-    constexpr int WPB = NTH / 64;
+    constexpr int NTH = 512;
     const int lane = threadIdx.x & 63;
-    const int wave_g = blockIdx.x * WPB + (threadIdx.x >> 6), nwaves = gridDim.x * WPB;
+    const int wave_g = blockIdx.x * 8 + (threadIdx.x >> 6), nwaves = gridDim.x * 8;
     const int RU = nb * N, RV = nb * M;
     float cr_row[RPW][SK_EPL], ct_row[RPW][SK_EPL];
-#pragma unroll
-    for (int q = 0; q < RPW; ++q) {
-        const int r = wave_g + q * nwaves;
-#pragma unroll
-        for (int k = 0; k < SK_EPL; ++k) {
-            const int l = lane + 64 * k;
-            cr_row[q][k] = (r < RU && l < M) ? pi_cr[(size_t)r * M + l] : -INFINITY;
-            ct_row[q][k] = (r < RV && l < N) ? crt[(size_t)r * N + l] : -INFINITY;
-        }
-    }
+    sk_reg_rows_load(cr_row, pi_cr, RU, M, wave_g, nwaves, lane);
+    sk_reg_rows_load(ct_row, crt, RV, N, wave_g, nwaves, lane);
     if (threadIdx.x == 0) s_fail = 0;
     const unsigned spin_limit = ctl->spin_limit;
     __syncthreads();
@@ -467,20 +234,7 @@ __global__ __launch_bounds__(NTH) void sk_persistent_tagged(float* __restrict__ 
         for (int q = 0; q < RPW; ++q) {
             const int r = wave_g + q * nwaves;
             if (r >= R) continue;
-            const float* pl = pot + (size_t)(r / rows_per_problem) * L;
-            float x[SK_EPL], mx = -INFINITY, s = 0.f;
-#pragma unroll
-            for (int k = 0; k < SK_EPL; ++k) {
-                const int l = lane + 64 * k;
-                x[k] = l < L ? cached[q][k] + pl[l] : -INFINITY;
-                mx = x[k] > mx ? x[k] : mx;
-            }
-            mx = wave_max(mx);
-#pragma unroll
-            for (int k = 0; k < SK_EPL; ++k)
-                if (lane + 64 * k < L) s += MathT<float>::exp(x[k] - mx);
-            s = wave_sum(s);
-            const float nv = logm[r] - (mx + MathT<float>::log(s));  // every lane holds the wave-wide mx and s
+            const float nv = logm[r] - sk_reg_row_lse(cached[q], pot + (size_t)(r / rows_per_problem) * L, L, lane);  // in every lane
             if (keep) own_u[q] = nv;
             if (lane == 0) {
                 __hip_atomic_store(tout + r, ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(nv),
@@ -512,14 +266,8 @@ __global__ __launch_bounds__(NTH) void sk_persistent_tagged(float* __restrict__ 
     for (int q = 0; q < RPW; ++q) {
         const int r = wave_g + q * nwaves;
         if (r >= RU) continue;
-        const float ui = own_u[q];
         const float* pl = pot + (size_t)(r / N) * M;
-        float* row = pi_cr + (size_t)r * M;
-#pragma unroll
-        for (int k = 0; k < SK_EPL; ++k) {
-            const int l = lane + 64 * k;
-            if (l < M) row[l] = MathT<float>::exp(ui + pl[l] + cr_row[q][k]);
-        }
+        sk_reg_row_plan(pi_cr + (size_t)r * M, cr_row[q], own_u[q], M, lane, [&](int l) { return pl[l]; });
     }
 }
 
@@ -542,8 +290,6 @@ __global__ __launch_bounds__(256) void sk_finish(SkCtl* ctl, T* __restrict__ pi,
     if (blockIdx.x == 0 && threadIdx.x == 0) ctl->iters = -1;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static unsigned sk_spin_limit() {
     if (const char* e = getenv("OTVAE_SK_SPIN_LIMIT")) {
         const long long q = atoll(e);
@@ -552,13 +298,52 @@ static unsigned sk_spin_limit() {
     return SK_SPIN_LIMIT;
 }
 
-// workgroups of `kernel` (NTH threads, `lds` bytes of dynamic LDS) the device can hold at once: a kernel whose
-// workgroups wait for each other must not be launched with more
-template <typename K>
-static int sk_resident_blocks(K kernel, int nth, size_t lds, int n_cu) {
+// Which solver a problem takes, from its shape alone.  Persistent: few LARGE workgroups (512 threads = 8 waves), up to 4 (fp32)
+// / 1 (fp64) rows of each matrix per wave in registers (2 x rpw x 16, x 2 for fp64, of the 256 a 512-thread workgroup has), the
+// potential (<= 16 KiB) through LDS.  Eligible when a row fits 16 registers per lane (N, M <= 1024) and the rows fit <= 128
+// workgroups.  One row per wave while that needs <= 128 workgroups.  Measured (1024 x 1024 fp32, 50 iterations, ms per solve):
+// launches 0.87; 512 threads x 1 row/wave (128 workgroups) 0.57, x 2 (64) 0.70, x 4 (32) 1.09; 1024 threads x 1 (64) 0.59;
+// 256 threads x 1 (256) 0.78 -- the rows a wave walks serially cost more than the extra barrier arrivals.
+struct SkRoute {
+    int rpw;      // rows of each matrix per wave; 0: one launch per half-iteration
+    int G;        // workgroups
+    bool tagged;  // fixed iteration count in fp32 (the training configuration): flag-in-data exchange, no barrier
+};
+static SkRoute sk_route(bool fp64, int nb, int N, int M, bool track) {
+    const long long rows = (long long)nb * (N > M ? N : M);
+    const int rpw_max = fp64 ? 1 : 4;
+    int rpw = 1;
+    while (rpw < rpw_max && rows > 1024LL * rpw) rpw *= 2;
+    if (N > 64 * SK_EPL || M > 64 * SK_EPL || rows > 1024LL * rpw) return SkRoute{0, 0, false};
+    return SkRoute{rpw, cdiv(rows, 8 * rpw), !fp64 && !track};
+}
+
+extern "C" int otvae_sinkhorn_route(int dtype, int nb, int N, int M, int tracked) {
+    if (nb <= 0 || N <= 0 || M <= 0 || dtype < 0 || dtype > 1) return -1;
+    const SkRoute r = sk_route(dtype == 1, nb, N, M, tracked != 0);
+    return r.rpw ? (r.tagged ? OTVAE_SK_ROUTE_FLAGS : OTVAE_SK_ROUTE_BARRIER) | r.rpw : OTVAE_SK_ROUTE_LAUNCHES;
+}
+
+// f(std::integral_constant<int, rpw>) for the rows per wave sk_route chooses from
+template <typename F>
+static bool sk_with_rpw(int rpw, F f) {
+    return rpw == 1 ? f(std::integral_constant<int, 1>{}) : rpw == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 4>{});
+}
+
+// Launches `kernel` on G workgroups of 512 threads with `lds` bytes of dynamic LDS, if the device can hold them all at once:
+// workgroups that wait for each other must not be launched otherwise (false: nothing was launched).
+template <typename K, typename... Args>
+static bool sk_launch_resident(K kernel, int G, size_t lds, hipStream_t st, Args... args) {
+    static int n_cu = 0;
+    if (n_cu == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) n_cu = v;
+        if (n_cu <= 0) n_cu = 1;
+    }
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nth, lds) != hipSuccess || per_cu <= 0) return 0;
-    return per_cu * n_cu;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 512, lds) != hipSuccess || per_cu * n_cu < G) return false;
+    kernel<<<G, 512, lds, st>>>(args...);
+    return true;
 }
 
 extern "C" int64_t otvae_sinkhorn_ws(int dtype, int nb, int N, int M) {
@@ -595,71 +380,17 @@ static int sinkhorn_impl(const T* a, const T* b, const T* Cm, int nb, int N, int
     sk_init_mat<T><<<dim3(cdiv(M, 32), cdiv(N, 32), nb), 256, 0, st>>>(Cm, N, M, (T)(1.0 / reg), pmax, P, pi, crt, a, b, loga, logb, u, v,
                                                                        ctl, track ? 0 : max_iter, sk_spin_limit(), tu, tv, cmax_out);
     OTVAE_CHECK_LAUNCH("otvae_sinkhorn_log(init)");
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) n_cu = v;
-        if (n_cu <= 0) n_cu = 1;
-    }
-    // Persistent solver: few LARGE workgroups (512 threads = 8 waves), up to 4 (fp32) / 1 (fp64) rows of each matrix per
-    // wave in registers, the potential through LDS.  Eligible when a row fits 16 registers per lane (N, M <= 1024), the
-    // rows fit <= 128 workgroups and the potentials fit the default 64 KiB of dynamic LDS.  OTVAE_SK_MULTILAUNCH=1 forces
-    // one launch per half-iteration; OTVAE_SK_PERSISTENT=256 selects the first-generation shape (one 256-thread workgroup
-    // per CU, one row per wave, no LDS staging), which measured 1.09 ms against 0.91 ms for the launches on the
-    // 1024 x 1024 fp32 problem; OTVAE_SK_RPW=n fixes the rows per wave (experiments).
-    const int rows = nb * (N > M ? N : M);
-    constexpr int RPWMAX = sizeof(T) == 4 ? 4 : 1;  // registers: 2 x RPW x 16 (x 2 for fp64) of the 256 a 512-thread workgroup has
-    const char* pers = getenv("OTVAE_SK_PERSISTENT");
-    const bool legacy = pers && atoi(pers) == 256;
-    int rpw = 1;
-    // One row per wave while that needs <= 128 workgroups.  Measured (1024 x 1024 fp32, 50 iterations, ms per solve):
-    // launches 0.87; 512 threads x 1 row/wave (128 workgroups) 0.57, x 2 (64) 0.70, x 4 (32) 1.09; 1024 threads x 1 (64)
-    // 0.59; 256 threads x 1 (256) 0.78 -- the rows a wave walks serially cost more than the extra barrier arrivals.
-    while (rpw < RPWMAX && cdiv(rows, 8 * rpw) > 128) rpw *= 2;
-    if (const char* e = getenv("OTVAE_SK_RPW")) {
-        const int want = atoi(e);
-        if (want == 1 || want == 2 || (want == 4 && RPWMAX == 4)) rpw = want;
-    }
-    const int G = cdiv(rows, 8 * rpw);
-    const size_t pot_bytes = (size_t)rows * sizeof(T);
-    bool eligible = N <= 64 * SK_EPL && M <= 64 * SK_EPL && G <= 128 && pot_bytes <= 60 * 1024;
-    if (eligible) {
-        // the workgroups of a persistent solve wait for each other: all G must be resident at once
-        int cap;
-        if (sizeof(T) == 4 && !track && !getenv("OTVAE_SK_BARRIER"))
-            cap = rpw == 1 ? sk_resident_blocks(sk_persistent_tagged<1, 512>, 512, pot_bytes, n_cu)
-                  : rpw == 2 ? sk_resident_blocks(sk_persistent_tagged<2, 512>, 512, pot_bytes, n_cu)
-                             : sk_resident_blocks(sk_persistent_tagged<4, 512>, 512, pot_bytes, n_cu);
-        else
-            cap = rpw == 1 ? sk_resident_blocks(sk_persistent<T, true, 1, 512, true>, 512, pot_bytes, n_cu)
-                  : rpw == 2 ? sk_resident_blocks(sk_persistent<T, true, 2, 512, true>, 512, pot_bytes, n_cu)
-                             : sk_resident_blocks(sk_persistent<T, true, RPWMAX, 512, true>, 512, pot_bytes, n_cu);
-        if (G > cap) eligible = false;
-    }
-    if (!getenv("OTVAE_SK_MULTILAUNCH") && (legacy || (eligible && !(pers && atoi(pers) == 0)))) {
-        if (legacy) {
-            int G1 = imax(1, imin(n_cu, cdiv(rows, 4)));
-            const bool cache = (nb * N <= 4 * G1) && (nb * M <= 4 * G1) && N <= 64 * SK_EPL && M <= 64 * SK_EPL;
-            if (cache)
-                sk_persistent<T, true, 1, 256, false><<<G1, 256, 0, st>>>(pi, crt, loga, logb, u, v, adu, adv, nb, N, M, max_iter, threshold, ctl);
-            else
-                sk_persistent<T, false, 1, 256, false><<<G1, 256, 0, st>>>(pi, crt, loga, logb, u, v, adu, adv, nb, N, M, max_iter, threshold, ctl);
-        } else if (sizeof(T) == 4 && !track && !getenv("OTVAE_SK_BARRIER")) {
-            // fixed iteration count in fp32 (the training configuration): flag-in-data exchange, no barrier
-            float* fpi = reinterpret_cast<float*>(pi);
-            const float *fcrt = reinterpret_cast<const float*>(crt), *fla = reinterpret_cast<const float*>(loga),
-                        *flb = reinterpret_cast<const float*>(logb);
-            float *fu = reinterpret_cast<float*>(u), *fv = reinterpret_cast<float*>(v);
-            if (rpw == 1) sk_persistent_tagged<1, 512><<<G, 512, pot_bytes, st>>>(fpi, fcrt, fla, flb, fu, fv, tu, tv, nb, N, M, max_iter, ctl);
-            else if (rpw == 2) sk_persistent_tagged<2, 512><<<G, 512, pot_bytes, st>>>(fpi, fcrt, fla, flb, fu, fv, tu, tv, nb, N, M, max_iter, ctl);
-            else sk_persistent_tagged<4, 512><<<G, 512, pot_bytes, st>>>(fpi, fcrt, fla, flb, fu, fv, tu, tv, nb, N, M, max_iter, ctl);
-        } else if (rpw == 1) {
-            sk_persistent<T, true, 1, 512, true><<<G, 512, pot_bytes, st>>>(pi, crt, loga, logb, u, v, adu, adv, nb, N, M, max_iter, threshold, ctl);
-        } else if (rpw == 2) {
-            sk_persistent<T, true, 2, 512, true><<<G, 512, pot_bytes, st>>>(pi, crt, loga, logb, u, v, adu, adv, nb, N, M, max_iter, threshold, ctl);
-        } else {
-            sk_persistent<T, true, RPWMAX, 512, true><<<G, 512, pot_bytes, st>>>(pi, crt, loga, logb, u, v, adu, adv, nb, N, M, max_iter, threshold, ctl);
-        }
+    const SkRoute route = getenv("OTVAE_SK_MULTILAUNCH") ? SkRoute{0, 0, false} : sk_route(sizeof(T) == 8, nb, N, M, track);
+    // the residency guard inside sk_launch_resident does not bind for an eligible shape on this hardware (include/otvae.h);
+    // where it would, the solve falls back to the launches
+    const bool persistent = route.rpw && sk_with_rpw(route.rpw, [&](auto c) {
+        constexpr int RPW = sizeof(T) == 4 ? decltype(c)::value : 1;
+        const size_t pot_bytes = (size_t)nb * (N > M ? N : M) * sizeof(T);
+        if constexpr (sizeof(T) == 4)
+            if (route.tagged) return sk_launch_resident(sk_persistent_tagged<RPW>, route.G, pot_bytes, st, pi, crt, loga, logb, u, v, tu, tv, nb, N, M, max_iter, ctl);
+        return sk_launch_resident(sk_persistent<T, RPW>, route.G, pot_bytes, st, pi, crt, loga, logb, u, v, adu, adv, nb, N, M, max_iter, threshold, ctl);
+    });
+    if (persistent) {
         OTVAE_CHECK_LAUNCH("otvae_sinkhorn_log(persistent)");
         sk_finish<T><<<64, 256, 0, st>>>(ctl, pi, (size_t)nb * N * M, u, (size_t)nb * N, v, (size_t)nb * M, iters_done);
         OTVAE_CHECK_LAUNCH("otvae_sinkhorn_log(finish)");
@@ -667,9 +398,9 @@ static int sinkhorn_impl(const T* a, const T* b, const T* Cm, int nb, int N, int
     } else {
         for (int it = 0; it < max_iter; ++it) {
             // v_j = log b_j - LSE_i(Cr_ij + u_i): rows of CrT
-            sk_pass<T><<<dim3(cdiv(M, 4), nb), 256, 0, st>>>(crt, u, logb, M, N, v, track ? adv : nullptr, ctl);
+            sk_pass<T><<<dim3(cdiv(M, 4), nb), 256, 0, st>>>(crt, u, logb, M, N, v, v, track ? adv : nullptr, ctl);
             // u_i = log a_i - LSE_j(Cr_ij + v_j): rows of Cr (held in pi)
-            sk_pass<T><<<dim3(cdiv(N, 4), nb), 256, 0, st>>>(pi, v, loga, N, M, u, track ? adu : nullptr, ctl);
+            sk_pass<T><<<dim3(cdiv(N, 4), nb), 256, 0, st>>>(pi, v, loga, N, M, u, u, track ? adu : nullptr, ctl);
             if (track) sk_check<T><<<1, 256, 0, st>>>(adu, adv, nb, N, M, threshold, ctl);
         }
         OTVAE_CHECK_LAUNCH("otvae_sinkhorn_log(iterations)");

@@ -1,7 +1,8 @@
 // Differentiable log-domain Sinkhorn: the reference's ``sinkhorn_log`` (ot/w2_utils.py:276-319) is plain torch arithmetic, so
 // autograd differentiates it THROUGH every iteration (with respect to a, b and C).  This file is that derivative as kernels:
 //
-//   forward  (otvae_sinkhorn_log_tape): the same iteration, one launch per half-iteration, every potential kept
+//   forward  (otvae_sinkhorn_log_tape): the solver's own kernels (sinkhorn_rows.h: sk_init_mat, sk_pass, sk_check), one launch per
+//            half-iteration, writing into a history instead of in place: every potential kept
 //            (u_0 = v_0 = 0, v_{i+1} = log b - LSE_n(Cr + u_i), u_{i+1} = log a - LSE_j(Cr + v_{i+1}), K' iterations done on the device's
 //            own stopping test), Cr and Cr^T kept;  pi = exp(u_K' + v_K' + Cr)
 //   backward (otvae_sinkhorn_log_bwd): the reverse sweep.  With G = gpi * pi, au[i] / av[i] the adjoints of u_i / v_i:
@@ -16,157 +17,38 @@
 //
 // This is the opt-in route (``sinkhorn_log`` called with inputs that require a gradient, ``SinkhornPrior(differentiate_plan=True)``);
 // the training default keeps the single-launch solver of sinkhorn.hip and the envelope gradient.
-#include "common.h"
+#include "sinkhorn_rows.h"
 
 namespace {
 
 template <typename T>
-struct M_;
-template <>
-struct M_<float> {
-    static __device__ __forceinline__ float exp(float x) { return __expf(x); }
-    static __device__ __forceinline__ float log(float x) { return __logf(x); }
-    static __device__ __forceinline__ float ninf() { return -INFINITY; }
-};
-template <>
-struct M_<double> {
-    static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
-    static __device__ __forceinline__ double log(double x) { return ::log(x); }
-    static __device__ __forceinline__ double ninf() { return -(double)INFINITY; }
-};
-
-struct TapeCtl {
-    int done;   // the stopping test fired
-    int iters;  // iterations performed (K')
-};
-
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-template <typename T>
 struct Tape {
-    T *cr, *crt, *loga, *logb, *adu, *adv, *uh, *vh;
-    TapeCtl* ctl;
+    T *cr, *crt, *loga, *logb, *adu, *adv, *uh, *vh;   // uh / vh: [K + 1][nb][N] / [K + 1][nb][M], slice 0 = the zero start
+    SkCtl* ctl;                                        // done and iters (K'); the tape's last 256 bytes
 };
 
 template <typename T>
 Tape<T> tape_layout(void* tape, int nb, int N, int M, int K) {
     char* w = (char*)tape;
     Tape<T> t;
-    const size_t mat = al256((size_t)nb * N * M * sizeof(T));
-    const size_t vn = al256((size_t)nb * N * sizeof(T)), vm = al256((size_t)nb * M * sizeof(T));
+    const size_t mat = align256((size_t)nb * N * M * sizeof(T));
+    const size_t vn = align256((size_t)nb * N * sizeof(T)), vm = align256((size_t)nb * M * sizeof(T));
     t.cr = (T*)w;   w += mat;
     t.crt = (T*)w;  w += mat;
     t.loga = (T*)w; w += vn;
     t.logb = (T*)w; w += vm;
     t.adu = (T*)w;  w += vn;
     t.adv = (T*)w;  w += vm;
-    t.uh = (T*)w;   w += al256((size_t)(K + 1) * nb * N * sizeof(T));
-    t.vh = (T*)w;   w += al256((size_t)(K + 1) * nb * M * sizeof(T));
-    t.ctl = (TapeCtl*)w;
+    t.uh = (T*)w;   w += align256((size_t)(K + 1) * nb * N * sizeof(T));
+    t.vh = (T*)w;   w += align256((size_t)(K + 1) * nb * M * sizeof(T));
+    t.ctl = (SkCtl*)w;
     return t;
 }
 
 size_t tape_bytes(int dtype, int nb, int N, int M, int K) {
     const size_t es = dtype ? 8 : 4;
-    return 2 * al256((size_t)nb * N * M * es) + 2 * (al256((size_t)nb * N * es) + al256((size_t)nb * M * es)) +
-           al256((size_t)(K + 1) * nb * N * es) + al256((size_t)(K + 1) * nb * M * es) + 256;
-}
-
-// Cr = -C / reg and its transpose (32 x 32 tiles through LDS), log marginals, u_0 = v_0 = 0, the control block
-template <typename T>
-__global__ __launch_bounds__(256) void tape_init(const T* __restrict__ Cm, int N, int M, T inv_reg, const T* __restrict__ a,
-                                                 const T* __restrict__ b, Tape<T> t, int preset_iters) {
-    __shared__ T tile[32][33];
-    const int pb = blockIdx.z;
-    const size_t boff = (size_t)pb * N * M;
-    const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int r = ty; r < 32; r += 8) {
-        const int i = i0 + r, j = j0 + tx;
-        if (i < N && j < M) {
-            const T val = Cm[boff + (size_t)i * M + j] * -inv_reg;   // the same product as sk_init_mat (sinkhorn.hip): identical Cr bits
-            t.cr[boff + (size_t)i * M + j] = val;
-            tile[r][tx] = val;
-        }
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const int j = j0 + r, i = i0 + tx;
-        if (i < N && j < M) t.crt[boff + (size_t)j * N + i] = tile[tx][r];
-    }
-    if (blockIdx.x == 0 && threadIdx.x < 32 && i0 + (int)threadIdx.x < N) {
-        const size_t i = (size_t)pb * N + i0 + threadIdx.x;
-        t.loga[i] = M_<T>::log((a ? a[i] : (T)1 / (T)N) + (T)1e-8);
-        t.uh[i] = (T)0;
-    }
-    if (blockIdx.y == 0 && threadIdx.x >= 64 && threadIdx.x < 96 && j0 + (int)threadIdx.x - 64 < M) {
-        const size_t j = (size_t)pb * M + j0 + threadIdx.x - 64;
-        t.logb[j] = M_<T>::log((b ? b[j] : (T)1 / (T)M) + (T)1e-8);
-        t.vh[j] = (T)0;
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 128) {
-        t.ctl->done = 0;
-        t.ctl->iters = preset_iters;
-    }
-}
-
-// out[r] = logm[r] - LSE_l(mat[r][l] + add[l]); absd[r] = |out[r] - prev[r]|.  One wave per row (the arithmetic of sk_pass).
-template <typename T>
-__global__ __launch_bounds__(256) void tape_pass(const T* __restrict__ mat, const T* __restrict__ add, const T* __restrict__ logm, int R,
-                                                 int L, const T* __restrict__ prev, T* __restrict__ out, T* __restrict__ absd,
-                                                 const TapeCtl* ctl) {
-    if (ctl->done) return;
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const int b = blockIdx.y;
-    const T* row = mat + ((size_t)b * R + r) * L;
-    const T* ad = add + (size_t)b * L;
-    T mx = M_<T>::ninf();
-    for (int l = lane; l < L; l += 64) {
-        const T x = row[l] + ad[l];
-        mx = x > mx ? x : mx;
-    }
-    mx = wave_max(mx);
-    T s = (T)0;
-    for (int l = lane; l < L; l += 64) s += M_<T>::exp(row[l] + ad[l] - mx);
-    s = wave_sum(s);
-    if (lane == 0) {
-        const T nv = logm[(size_t)b * R + r] - (mx + M_<T>::log(s));
-        out[(size_t)b * R + r] = nv;
-        if (absd) {
-            const T d = nv - prev[(size_t)b * R + r];
-            absd[(size_t)b * R + r] = d < (T)0 ? -d : d;
-        }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void tape_check(const T* __restrict__ adu, const T* __restrict__ adv, int nb, int N, int M,
-                                                  double threshold, int track, TapeCtl* ctl) {
-    __shared__ double red[4];
-    __shared__ double best;
-    if (ctl->done) return;
-    if (!track) return;
-    if (threadIdx.x == 0) best = INFINITY;
-    __syncthreads();
-    for (int b = 0; b < nb; ++b) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < N; i += 256) s += (double)adu[(size_t)b * N + i];
-        for (int i = threadIdx.x; i < M; i += 256) s += (double)adv[(size_t)b * M + i];
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const T d = (T)((red[0] + red[1]) + (red[2] + red[3]));  // the reference sums in the tensor dtype
-            if ((double)d < best) best = (double)d;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ctl->iters += 1;
-        if (best < threshold) ctl->done = 1;
-    }
+    return 2 * align256((size_t)nb * N * M * es) + 2 * (align256((size_t)nb * N * es) + align256((size_t)nb * M * es)) +
+           align256((size_t)(K + 1) * nb * N * es) + align256((size_t)(K + 1) * nb * M * es) + 256;
 }
 
 // pi = exp(u_K' + v_K' + Cr); the first block column also copies the final potentials out
@@ -180,7 +62,7 @@ __global__ __launch_bounds__(256) void tape_pi(Tape<T> t, int nb, int N, int M, 
     const size_t boff = (size_t)b * N * M, total = (size_t)N * M;
     for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
         const int i = e / M, j = e - (size_t)i * M;
-        pi[boff + e] = M_<T>::exp(u[i] + v[j] + t.cr[boff + e]);
+        pi[boff + e] = MathT<T>::exp(u[i] + v[j] + t.cr[boff + e]);
     }
     if (blockIdx.x == 0) {
         if (u_out) for (int i = threadIdx.x; i < N; i += 256) u_out[(size_t)b * N + i] = u[i];
@@ -198,7 +80,7 @@ __global__ __launch_bounds__(256) void zero_kernel(T* __restrict__ p, size_t n) 
 // au[K'][n] = sum_j gpi[n][j] pi[n][j]   (one wave per row)
 template <typename T>
 __global__ __launch_bounds__(256) void bwd_rowsum(const T* __restrict__ gpi, const T* __restrict__ pi, int nb, int N, int M,
-                                                  const TapeCtl* ctl, T* __restrict__ auh) {
+                                                  const SkCtl* ctl, T* __restrict__ auh) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= N) return;
@@ -227,7 +109,7 @@ __global__ __launch_bounds__(256) void bwd_colsum(const T* __restrict__ gpi, con
     part[((size_t)ch * nb + b) * M + j] = s;
 }
 template <typename T>
-__global__ __launch_bounds__(256) void bwd_colsum_final(const T* __restrict__ part, int nb, int M, const TapeCtl* ctl, T* __restrict__ avh) {
+__global__ __launch_bounds__(256) void bwd_colsum_final(const T* __restrict__ part, int nb, int M, const SkCtl* ctl, T* __restrict__ avh) {
     const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (j >= M) return;
     T s = (T)0;
@@ -239,7 +121,7 @@ __global__ __launch_bounds__(256) void bwd_colsum_final(const T* __restrict__ pa
 template <typename T>
 __global__ __launch_bounds__(256) void bwd_pass(const T* __restrict__ mat, int R, int L, const T* __restrict__ adj, const T* __restrict__ pot,
                                                 const T* __restrict__ logm, const T* __restrict__ rowpot, const T* acc, T* out,
-                                                int it, const TapeCtl* ctl) {
+                                                int it, const SkCtl* ctl) {
     if (it >= ctl->iters) return;
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -249,7 +131,7 @@ __global__ __launch_bounds__(256) void bwd_pass(const T* __restrict__ mat, int R
     const size_t lo = (size_t)b * L;
     const T rp = rowpot[(size_t)b * R + r];
     T s = (T)0;
-    for (int l = lane; l < L; l += 64) s += adj[lo + l] * M_<T>::exp(row[l] + pot[lo + l] - logm[lo + l] + rp);
+    for (int l = lane; l < L; l += 64) s += adj[lo + l] * MathT<T>::exp(row[l] + pot[lo + l] - logm[lo + l] + rp);
     s = wave_sum(s);
     if (lane == 0) out[(size_t)b * R + r] = (acc ? acc[(size_t)b * R + r] : (T)0) - s;
 }
@@ -286,8 +168,8 @@ __global__ __launch_bounds__(256) void bwd_final(const T* __restrict__ gpi, cons
         }
         __syncthreads();
         if (in) {
-            acc -= rowv[1][ty] * M_<T>::exp(cr + colv[0][tx] + rowv[0][ty]);
-            acc -= colv[1][tx] * M_<T>::exp(cr + rowv[2][ty] + colv[0][tx] - colv[2][tx]);
+            acc -= rowv[1][ty] * MathT<T>::exp(cr + colv[0][tx] + rowv[0][ty]);
+            acc -= colv[1][tx] * MathT<T>::exp(cr + rowv[2][ty] + colv[0][tx] - colv[2][tx]);
         }
     }
     if (in) gC[e] = -inv_reg * acc;
@@ -296,7 +178,7 @@ __global__ __launch_bounds__(256) void bwd_final(const T* __restrict__ gpi, cons
 // g[r] = (sum_{i=1..K'} adj[i][r]) / (marg[r] + 1e-8)
 template <typename T>
 __global__ __launch_bounds__(256) void bwd_marginal(const T* __restrict__ adjh, const T* __restrict__ marg, int nb, int R,
-                                                    const TapeCtl* ctl, T* __restrict__ g) {
+                                                    const SkCtl* ctl, T* __restrict__ g) {
     const int r = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (r >= R) return;
     const int K = ctl->iters;
@@ -310,14 +192,17 @@ int tape_forward(const T* a, const T* b, const T* Cm, int nb, int N, int M, doub
                  T* v, int32_t* iters_done, hipStream_t st) {
     Tape<T> t = tape_layout<T>(tape, nb, N, M, K);
     const bool track = threshold > 0.0;
-    tape_init<T><<<dim3(cdiv(M, 32), cdiv(N, 32), nb), 256, 0, st>>>(Cm, N, M, (T)(1.0 / reg), a, b, t, track ? 0 : K);
+    // no cost maximum, no tagged potentials; u_0 = v_0 = 0 into history slice 0
+    sk_init_mat<T><<<dim3(cdiv(M, 32), cdiv(N, 32), nb), 256, 0, st>>>(Cm, N, M, (T)(1.0 / reg), (const T*)nullptr, 0, t.cr, t.crt, a, b, t.loga,
+                                                                       t.logb, t.uh, t.vh, t.ctl, track ? 0 : K, 0u, nullptr, nullptr,
+                                                                       (T*)nullptr);
     OTVAE_CHECK_LAUNCH("otvae_sinkhorn_log_tape(init)");
     for (int i = 0; i < K; ++i) {
         const T *ui = t.uh + (size_t)i * nb * N, *vi = t.vh + (size_t)i * nb * M;
         T *un = t.uh + (size_t)(i + 1) * nb * N, *vn = t.vh + (size_t)(i + 1) * nb * M;
-        tape_pass<T><<<dim3(cdiv(M, 4), nb), 256, 0, st>>>(t.crt, ui, t.logb, M, N, vi, vn, track ? t.adv : nullptr, t.ctl);
-        tape_pass<T><<<dim3(cdiv(N, 4), nb), 256, 0, st>>>(t.cr, vn, t.loga, N, M, ui, un, track ? t.adu : nullptr, t.ctl);
-        if (track) tape_check<T><<<1, 256, 0, st>>>(t.adu, t.adv, nb, N, M, threshold, 1, t.ctl);
+        sk_pass<T><<<dim3(cdiv(M, 4), nb), 256, 0, st>>>(t.crt, ui, t.logb, M, N, vi, vn, track ? t.adv : nullptr, t.ctl);
+        sk_pass<T><<<dim3(cdiv(N, 4), nb), 256, 0, st>>>(t.cr, vn, t.loga, N, M, ui, un, track ? t.adu : nullptr, t.ctl);
+        if (track) sk_check<T><<<1, 256, 0, st>>>(t.adu, t.adv, nb, N, M, threshold, t.ctl);
     }
     OTVAE_CHECK_LAUNCH("otvae_sinkhorn_log_tape(iterations)");
     tape_pi<T><<<dim3(imin(cdiv((int64_t)N * M, 256), 1024), nb), 256, 0, st>>>(t, nb, N, M, pi, u, v, iters_done);
@@ -332,11 +217,11 @@ int tape_backward(const T* gpi, const T* pi, const T* a, const T* b, int nb, int
     char* w = (char*)ws;
     const size_t nau = (size_t)(K + 1) * nb * N, nav = (size_t)(K + 1) * nb * M;
     T* auh = (T*)w;
-    w += al256(nau * sizeof(T));
+    w += align256(nau * sizeof(T));
     T* avh = (T*)w;
-    w += al256(nav * sizeof(T));
+    w += align256(nav * sizeof(T));
     T* part = (T*)w;
-    const size_t nz = (al256(nau * sizeof(T)) + al256(nav * sizeof(T))) / sizeof(T);   // both adjoint histories, contiguous
+    const size_t nz = (align256(nau * sizeof(T)) + align256(nav * sizeof(T))) / sizeof(T);   // both adjoint histories, contiguous
     zero_kernel<T><<<imin(cdiv((int64_t)nz, 256), 1024), 256, 0, st>>>(auh, nz);
     bwd_rowsum<T><<<dim3(cdiv(N, 4), nb), 256, 0, st>>>(gpi, pi, nb, N, M, t.ctl, auh);
     bwd_colsum<T><<<dim3(cdiv(M, 256), COL_CHUNKS, nb), 256, 0, st>>>(gpi, pi, nb, N, M, part);
@@ -372,8 +257,8 @@ extern "C" int64_t otvae_sinkhorn_tape_bytes(int dtype, int nb, int N, int M, in
 extern "C" int64_t otvae_sinkhorn_bwd_ws(int dtype, int nb, int N, int M, int max_iter) {
     if (nb <= 0 || N <= 0 || M <= 0 || max_iter < 0 || dtype < 0 || dtype > 1) return -1;
     const size_t es = dtype ? 8 : 4;
-    return (int64_t)(al256((size_t)(max_iter + 1) * nb * N * es) + al256((size_t)(max_iter + 1) * nb * M * es) +
-                     al256((size_t)COL_CHUNKS * nb * M * es) + 256);
+    return (int64_t)(align256((size_t)(max_iter + 1) * nb * N * es) + align256((size_t)(max_iter + 1) * nb * M * es) +
+                     align256((size_t)COL_CHUNKS * nb * M * es) + 256);
 }
 
 extern "C" int otvae_sinkhorn_log_tape(int dtype, const void* a, const void* b, const void* C, int nb, int N, int M, double reg,

@@ -66,6 +66,37 @@ def test_library_exports_every_declared_symbol(lib_path):
     assert lib.otvae_abi_version() == 2
 
 
+def test_sinkhorn_route_by_shape(lib_path):
+    """``otvae_sinkhorn_route`` (host only: no device query, no environment): launches, or exchange | rows per wave, from
+    rows = nb * max(N, M): 1 row per wave up to 1024 rows, 2 up to 2048, 4 up to 4096 (fp32 only; fp64 stops at 1024), N, M <= 1024;
+    fp32 takes the flag-in-data exchange with a fixed iteration count and the barrier when the stopping test is tracked."""
+    lib = ctypes.CDLL(lib_path)
+    route = lib.otvae_sinkhorn_route
+    route.restype, route.argtypes = ctypes.c_int, [ctypes.c_int] * 5
+    LAUNCHES, BARRIER, FLAGS = 0, 0x10, 0x20
+    F32, F64 = 0, 1
+    for dtype, nb, n, m, tracked, want in [
+            # the shapes of test_sinkhorn_persistent_equals_multilaunch
+            (F32, 1, 1024, 1024, 0, FLAGS | 1), (F32, 1, 256, 256, 0, FLAGS | 1), (F32, 3, 200, 300, 0, FLAGS | 1),
+            (F32, 1, 64, 1000, 0, FLAGS | 1), (F64, 1, 100, 37, 1, BARRIER | 1), (F32, 6, 33, 65, 1, BARRIER | 1),
+            (F64, 1, 1024, 1024, 0, BARRIER | 1), (F32, 1, 1500, 700, 0, LAUNCHES), (F64, 1, 7, 5, 0, BARRIER | 1),
+            (F32, 2, 600, 1000, 0, FLAGS | 2), (F32, 4, 1000, 900, 0, FLAGS | 4), (F32, 2, 1000, 600, 1, BARRIER | 2),
+            (F32, 3, 700, 1000, 1, BARRIER | 4), (F32, 5, 1000, 1000, 0, LAUNCHES), (F64, 2, 600, 600, 0, LAUNCHES),
+            # rows = 1024 / 1025 / 2048 / 2049 / 4096 / 4097
+            (F32, 2, 512, 100, 0, FLAGS | 1), (F32, 41, 20, 25, 0, FLAGS | 2), (F32, 5, 205, 100, 1, BARRIER | 2),
+            (F32, 2, 1024, 1024, 0, FLAGS | 2), (F32, 3, 683, 10, 0, FLAGS | 4), (F32, 4, 1024, 1024, 0, FLAGS | 4),
+            (F32, 17, 241, 241, 0, LAUNCHES),
+            # N or M = 1024 / 1025, either side
+            (F32, 1, 1024, 5, 0, FLAGS | 1), (F32, 1, 5, 1024, 1, BARRIER | 1), (F32, 1, 1025, 5, 0, LAUNCHES), (F32, 1, 5, 1025, 1, LAUNCHES),
+            # fp64 at 1024 / 1025 rows, tracked or not: the barrier, one row per wave
+            (F64, 4, 256, 200, 0, BARRIER | 1), (F64, 4, 256, 200, 1, BARRIER | 1), (F64, 5, 205, 100, 0, LAUNCHES), (F64, 5, 205, 100, 1, LAUNCHES),
+            # `tracked` moves fp32 from flag-in-data to the barrier at every rows-per-wave count
+            (F32, 1, 1024, 1024, 1, BARRIER | 1), (F32, 2, 1024, 1024, 1, BARRIER | 2), (F32, 4, 1024, 1024, 1, BARRIER | 4),
+            # bad arguments
+            (2, 1, 8, 8, 0, -1), (F32, 0, 8, 8, 0, -1), (F32, 1, 0, 8, 0, -1), (F32, 1, 8, -1, 0, -1)]:
+        assert route(dtype, nb, n, m, tracked) == want, (dtype, nb, n, m, tracked, route(dtype, nb, n, m, tracked), want)
+
+
 def test_library_contains_gfx950_code_object(lib_path):
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", lib_path], capture_output=True, text=True)
     blob = open(lib_path, "rb").read()

@@ -1550,25 +1550,37 @@ def test_gaussian_transport_1024_dims_vs_oracle(A):
 
 def test_sinkhorn_persistent_equals_multilaunch(A):
     """The one-launch solvers (rows in registers, the potential in LDS: the flag-in-data exchange that fp32 problems with
-    a fixed iteration count take by default, the grid-barrier exchange (OTVAE_SK_BARRIER, and whenever an early exit is
-    tracked), each rows-per-wave variant, the first-generation 256-thread shape) and the launch-per-half-iteration solver
-    run the same arithmetic per row: plan, potentials and iteration count must be identical bits, including the early
-    exit.  Problems the persistent shapes cannot hold (rows > 1024, more rows than 128 workgroups take) fall back to
-    launches by themselves."""
+    a fixed iteration count take, the grid-barrier exchange (fp64, and whenever an early exit is tracked), each with every
+    rows-per-wave count) and the launch-per-half-iteration solver run the same arithmetic per row: plan, potentials and
+    iteration count must be identical bits, including the early exit.  Problems the persistent shapes cannot hold (rows
+    > 1024 long, more rows than 128 workgroups take) go to the launches by themselves.  ``otvae_sinkhorn_route`` tells
+    which route a shape takes: every case is held to the one its comment names, and the list to covering them all."""
     import os
+    from ot_vae_lightning_amd import _lib
     from ot_vae_lightning_amd.ot import w2_utils as W
-    cases = [((), 1024, 1024, torch.float32, 0.05, 50, 0.0),      # bench shape: 1 row per wave, 128 workgroups
-             ((), 256, 256, torch.float32, 0.05, 50, 0.0),         # CIFAR per-GPU batch: 1 row per wave
-             ((3,), 200, 300, torch.float32, 0.05, 7, 0.0),        # batched, non-square, fixed count: flag-in-data, 2 rows/wave
-             ((), 64, 1000, torch.float32, 0.05, 0, 0.0),          # no iteration, flag-in-data plan
-             ((), 100, 37, torch.float64, 0.1, 200, 1e-9),         # non-square, early exit
-             ((2, 3), 33, 65, torch.float32, 0.05, 300, 1e-3),     # batched: min-over-batch early exit
-             ((), 1024, 1024, torch.float64, 0.05, 10, 0.0),       # fp64 at the bench shape: 128 workgroups
-             ((), 1500, 700, torch.float32, 0.05, 20, 0.0),        # rows > 1024: not register-resident
-             ((), 7, 5, torch.float64, 1.0, 0, 0.0)]               # no iteration at all
-    variants = [{}, {"OTVAE_SK_RPW": "2"}, {"OTVAE_SK_RPW": "4"}, {"OTVAE_SK_BARRIER": "1"}, {"OTVAE_SK_BARRIER": "1", "OTVAE_SK_RPW": "2"},
-                {"OTVAE_SK_PERSISTENT": "256"}]
-    for lead, n, m, dt, reg, it, thr in cases:
+    LAUNCHES, BARRIER, FLAGS = 0, 0x10, 0x20   # include/otvae.h: OTVAE_SK_ROUTE_*, or-ed with the rows per wave
+    f32, f64 = torch.float32, torch.float64
+    cases = [((), 1024, 1024, f32, 0.05, 50, 0.0, FLAGS | 1),      # bench shape: 1 row per wave, 128 workgroups
+             ((), 256, 256, f32, 0.05, 50, 0.0, FLAGS | 1),        # CIFAR per-GPU batch: 1 row per wave
+             ((3,), 200, 300, f32, 0.05, 7, 0.0, FLAGS | 1),       # batched, non-square, fixed count: 900 rows, 1 row per wave
+             ((), 64, 1000, f32, 0.05, 0, 0.0, FLAGS | 1),         # no iteration, flag-in-data plan
+             ((), 100, 37, f64, 0.1, 200, 1e-9, BARRIER | 1),      # non-square, early exit
+             ((2, 3), 33, 65, f32, 0.05, 300, 1e-3, BARRIER | 1),  # batched: min-over-batch early exit, fp32 tracked
+             ((), 1024, 1024, f64, 0.05, 10, 0.0, BARRIER | 1),    # fp64 at the bench shape, untracked: 128 workgroups
+             ((), 1500, 700, f32, 0.05, 20, 0.0, LAUNCHES),        # rows > 1024 long: not register-resident
+             ((), 7, 5, f64, 1.0, 0, 0.0, BARRIER | 1),            # no iteration at all
+             ((2,), 600, 1000, f32, 0.05, 7, 0.0, FLAGS | 2),      # 2000 rows: flag-in-data, 2 rows/wave, 125 workgroups
+             ((4,), 1000, 900, f32, 0.05, 5, 0.0, FLAGS | 4),      # 4000 rows: flag-in-data, 4 rows/wave, 125 workgroups
+             ((2,), 1000, 600, f32, 0.05, 300, 1e-3, BARRIER | 2), # 2000 rows, tracked: barrier, 2 rows/wave
+             ((3,), 700, 1000, f32, 0.05, 300, 1e-3, BARRIER | 4), # 3000 rows, tracked: barrier, 4 rows/wave, 94 workgroups
+             ((5,), 1000, 1000, f32, 0.05, 5, 0.0, LAUNCHES),      # 5000 rows: too many for 128 workgroups
+             ((2,), 600, 600, f64, 0.1, 5, 0.0, LAUNCHES)]         # 1200 rows: too many for fp64 (1 row per wave only)
+    # everything the dispatcher can produce: both exchanges x {1, 2, 4} rows per wave in fp32, the barrier x 1 in fp64, launches in both
+    want = {(f32, LAUNCHES), (f64, LAUNCHES), (f64, BARRIER | 1)} | {(f32, x | r) for x in (BARRIER, FLAGS) for r in (1, 2, 4)}
+    assert {(c[3], c[7]) for c in cases} == want
+    lib = _lib.load()
+    for lead, n, m, dt, reg, it, thr, route in cases:
+        assert lib.otvae_sinkhorn_route(int(dt == f64), math.prod(lead), n, m, int(thr > 0)) == route, (lead, n, m)
         a, b, C = _sinkhorn_problem(lead, n, m, dt, seed=n + m)
         a, b, C = a.cuda(), b.cuda(), C.cuda()
         if dt == torch.float32 and reg < 0.1:
@@ -1578,18 +1590,40 @@ def test_sinkhorn_persistent_equals_multilaunch(A):
             ref = W.sinkhorn_log_potentials(a, b, C, reg=reg, max_iter=it, threshold=thr)
         finally:
             del os.environ["OTVAE_SK_MULTILAUNCH"]
-        for env in variants:
-            os.environ.update(env)
-            try:
-                got = W.sinkhorn_log_potentials(a, b, C, reg=reg, max_iter=it, threshold=thr)
-            finally:
-                for k in env:
-                    del os.environ[k]
-            torch.cuda.synchronize()
-            assert int(got[3]) == int(ref[3]) and int(got[3]) >= 0, (n, m, env, int(got[3]), int(ref[3]))
-            for g, r, name in zip(got[:3], ref[:3], ("pi", "u", "v")):
-                assert torch.equal(g, r), (n, m, env, name, float((g - r).abs().max()))
-            assert torch.isfinite(got[0]).all()
+        got = W.sinkhorn_log_potentials(a, b, C, reg=reg, max_iter=it, threshold=thr)
+        torch.cuda.synchronize()
+        assert int(got[3]) == int(ref[3]) and int(got[3]) >= 0, (n, m, int(got[3]), int(ref[3]))
+        for g, r, name in zip(got[:3], ref[:3], ("pi", "u", "v")):
+            assert torch.equal(g, r), (n, m, name, float((g - r).abs().max()))
+        assert torch.isfinite(got[0]).all()
+
+
+@pytest.mark.parametrize("lead,n,m,dt,reg,it,thr", [((), 7, 5, torch.float64, 1.0, 0, 0.0),               # no iteration at all
+                                                    ((2, 3), 33, 65, torch.float32, 0.05, 300, 1e-3),     # min-over-batch early exit
+                                                    ((), 200, 300, torch.float32, 0.05, 7, 0.0)])         # fixed count, non-square
+def test_sinkhorn_tape_forward_equals_multilaunch_solver(A, monkeypatch, lead, n, m, dt, reg, it, thr):
+    """The tape-recording forward (``sinkhorn_log`` with a cost that requires a gradient) and the launch-per-half-iteration
+    solver run the same kernels: identical plan bits and the same iteration count."""
+    from ot_vae_lightning_amd import _lib
+    from ot_vae_lightning_amd.ot import w2_utils as W
+    a, b, C = (t.cuda() for t in _sinkhorn_problem(lead, n, m, dt, seed=n + m))
+    monkeypatch.setenv("OTVAE_SK_MULTILAUNCH", "1")
+    ref = W.sinkhorn_log_potentials(a, b, C, reg=reg, max_iter=it, threshold=thr)
+    monkeypatch.delenv("OTVAE_SK_MULTILAUNCH")
+    pi = W.sinkhorn_log(a, b, C.clone().requires_grad_(), reg=reg, max_iter=it, threshold=thr)
+    assert pi.grad_fn is not None
+    assert torch.equal(pi.detach(), ref[0]), float((pi.detach() - ref[0]).abs().max())
+    # the iteration count the tape forward stopped at (sinkhorn_log does not return it): the entry point itself
+    lib, nb = _lib.load(), max(1, math.prod(lead))
+    a2, b2, c3 = a.expand(*lead, n).reshape(nb, n).contiguous(), b.expand(*lead, m).reshape(nb, m).contiguous(), C.reshape(nb, n, m)
+    tape = torch.empty(lib.otvae_sinkhorn_tape_bytes(W._dt(C), nb, n, m, it), device="cuda", dtype=torch.uint8)
+    pi2, u2, v2 = torch.empty_like(c3), torch.empty_like(a2), torch.empty_like(b2)
+    iters = torch.zeros(1, device="cuda", dtype=torch.int32)
+    _lib.check(lib.otvae_sinkhorn_log_tape(W._dt(C), _lib.ptr(a2), _lib.ptr(b2), _lib.ptr(c3), nb, n, m, reg, it, thr, _lib.ptr(tape),
+                                           _lib.ptr(pi2), _lib.ptr(u2), _lib.ptr(v2), _lib.ptr(iters), _lib.stream()), "tape")
+    assert int(iters) == int(ref[3]) and int(iters) >= 0, (int(iters), int(ref[3]))
+    for g, r in zip((pi2, u2, v2), ref[:3]):
+        assert torch.equal(g.reshape(r.shape), r)
 
 
 # ------------------------------------------------------------------------------------------------ G9 codebook k-means
