@@ -694,6 +694,55 @@ int64_t otvae_ssim_grad_ws(int B, int C, int H, int W, int kh, int kw); /* bytes
 int otvae_ssim_grad(int in_dtype, const void* preds, const void* target, int B, int C, int H, int W, int kh, int kw, const double* wh,
                     const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi, const double* g,
                     void* grad_preds, void* ws, void* stream);
+/* MultiScaleStructuralSimilarityIndexMeasure's accumulation (csrc/ms_ssim.hip; metrics/ms_ssim.py): otvae_ssim_accum's map, window,
+ * in_dtype, range_mode and state layout, over S scales.  With p_0 = preds, t_0 = target and scale s on [B][C][H >> s][W >> s],
+ *   cs   = (2 s_pt + c2) / (s_pp + s_tt + c2),   ssim = (2 mu_p mu_t + c1) / (mu_p^2 + mu_t^2 + c1) * cs    at every valid position,
+ *   v_s[b] = the mean over C and all positions of cs for s < S - 1, of ssim for s = S - 1,
+ *   p_{s+1} = the 2 x 2, stride-2 average of p_s (a trailing odd row / column dropped; always of the UNCLAMPED values), t likewise,
+ *   msssim_b = prod_s f(v_s[b])^betas[s],   f = identity (normalize 0; a negative v_s gives NaN), relu (1) or (v + 1) / 2 (2).
+ * One launch per scale: it reads the scale's pair once, leaves {sum cs, sum ssim} per workgroup in ws and writes the next scale's pair
+ * into the pyramids (each pooled element exactly once, in in_dtype); then a one-workgroup fold over all scales in a fixed order.
+ * range_mode 1 clamps each scale's images at the load; range_mode 2 takes R per scale from that scale's two images (one more launch
+ * per scale).  per_image (nullable) [B] receives msssim_b; w (nullable) [S][B] receives w_s[b] = d msssim_b / d v_s[b] =
+ * betas[s] msssim_b f'(v_s) / f(v_s), and 0 where f(v_s[b]) = 0 under normalize 1 / 2: a dead image passes no gradient.  (A deliberate
+ * rule: the composed formula meets 0 * inf there, which autograd turns into NaN or into 0 depending on how the derivative of relu is
+ * written.)  state[0] += sum_b msssim_b, state[1] += B.  No atomics, no host read; msssim_b, w_.[b] and image b's
+ * pooled images depend on image b alone, bit for bit, whatever B is (range_mode 2 excepted).
+ * betas: HOST array [S].  state: otvae_ms_ssim_state_words() doubles, laid out as otvae_ssim_accum's; a fresh state is all zeros.
+ * pyr_preds / pyr_target: otvae_ms_ssim_pyramid(in_dtype, B, C, H, W, S) bytes each -- scales 1 .. S - 1 of the image, one after the
+ * other; written here, read by otvae_ms_ssim_grad (both may be NULL when S = 1).
+ * ws: otvae_ms_ssim_ws(B, C, H, W, kh, kw, S) bytes -- two doubles per (scale, image, channel, 16 x 32 tile of positions).
+ * OTVAE_EINVAL: as otvae_ssim_accum, S < 1, normalize outside 0 .. 2, and a scale smaller than the window: H >> (S - 1) < kh or
+ * W >> (S - 1) < kw.  OTVAE_EUNSUPPORTED (the size queries: -1, as for every refused argument): S > 8, more than 31 taps on an axis,
+ * 2^31 or more tiles or plane elements. */
+int otvae_ms_ssim_state_words(void);
+int64_t otvae_ms_ssim_pyramid(int in_dtype, int B, int C, int H, int W, int S);   /* bytes per image tensor; -1: refused arguments */
+int64_t otvae_ms_ssim_ws(int B, int C, int H, int W, int kh, int kw, int S);      /* bytes; -1: refused arguments */
+int otvae_ms_ssim_accum(int in_dtype, const void* preds, const void* target, int B, int C, int H, int W, int kh, int kw,
+                        const double* wh, const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi,
+                        int S, const double* betas, int normalize, double* per_image, double* w, void* pyr_preds, void* pyr_target,
+                        double* state, void* ws, void* stream);
+/* The gradient of otvae_ms_ssim_accum's per-image values (csrc/ms_ssim.hip; losses.py's MSSSIMLoss): with an upstream cotangent g[b]
+ * (DEVICE array, fp64) on msssim_b, the weights w [S][B] and the pyramids that call left, and n_s = C (H_s - kh + 1) (W_s - kw + 1),
+ *   d/dp_s[q] = own_s(q) + 1/4 d/dp_{s+1}[q >> 1]   (no second term at the last scale, nor under a dropped odd row / column),
+ *   own_s(q) = alpha(q) + 2 p_q beta(q) + t_q gamma(q),   alpha, beta, gamma = W^T[(g_b w_s[b] / n_s) (a, b, c)]
+ * in otvae_ssim_grad's notation; a, b, c are the ones documented there at the last scale and, for the cs scales s < S - 1,
+ *   a = 2 (cs mu_p - mu_t) / B2,  b = -cs / B2,  c = 2 / B2      (the same formula with A1 = B1 = 1).
+ * One launch per scale from the coarsest to the finest, each built like otvae_ssim_grad's and evaluated about a pixel of the tile.
+ * grad_preds [B][C][H][W] in in_dtype: EVERY element is written, nothing need be zeroed; fixed summation order, no atomics, no host
+ * read; image b's gradient depends on image b, g[b] and w_.[b] alone, bit for bit.  range_mode 0 and 1 only; in mode 1 the OWN term of
+ * a scale is 0 where that scale's preds pixel lies strictly outside [range_lo, range_hi]; the coarser scales' gradient always passes
+ * (the pooling took the unclamped values).  The gradient for target is the same call with preds / target and the two pyramids
+ * exchanged (every term is symmetric).
+ * ws: otvae_ms_ssim_grad_ws(in_dtype, B, C, H, W, kh, kw, S) bytes -- the gradients of scales 1 .. S - 1, alternating between two
+ * buffers (0 bytes at S = 1; ws may then be NULL).
+ * OTVAE_EINVAL: as otvae_ms_ssim_accum, and range_mode 2.  OTVAE_EUNSUPPORTED (otvae_ms_ssim_grad_ws: -1): S > 8, more than 15 taps
+ * on an axis, 2^31 or more tiles or plane elements. */
+int64_t otvae_ms_ssim_grad_ws(int in_dtype, int B, int C, int H, int W, int kh, int kw, int S); /* bytes; -1: refused arguments */
+int otvae_ms_ssim_grad(int in_dtype, const void* preds, const void* target, const void* pyr_preds, const void* pyr_target, int B, int C,
+                       int H, int W, int kh, int kw, const double* wh, const double* ww, double k1, double k2, int range_mode,
+                       double range_lo, double range_hi, int S, const double* g, const double* w, void* grad_preds, void* ws,
+                       void* stream);
 /* Kernel Inception Distance (csrc/kid.hip; metrics/kid.py): the unbiased polynomial-kernel MMD^2 of S subsets of m rows each, in one
  * entry.  real [n_real][D], fake [n_fake][D] fp32 row-major; idx_real / idx_fake [S][m] (device, int32; both NULL: every subset is
  * rows 0 .. m - 1).  For subset s, x_i = real[idx_real[s][i]], y_j = fake[idx_fake[s][j]], k(a, b) = (gamma <a, b> + coef)^degree:

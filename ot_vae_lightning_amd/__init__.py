@@ -11,6 +11,7 @@ from .engine import *  # noqa: F401,F403
 from . import metrics  # noqa: F401
 from . import losses  # noqa: F401
 from .losses import *  # noqa: F401,F403
+from .losses import MSSSIMLoss, ms_ssim_loss  # noqa: F401
 from . import transforms  # noqa: F401
 from .transforms import *  # noqa: F401,F403
 from .utils import Collage  # noqa: F401

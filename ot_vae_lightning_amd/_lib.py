@@ -176,6 +176,14 @@ SIGNATURES = {
     "otvae_ssim_accum": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, vp, vp, vp, vp]),
     "otvae_ssim_grad_ws": (i64, [i32, i32, i32, i32, i32, i32]),
     "otvae_ssim_grad": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, vp, vp, vp, vp]),
+    "otvae_ms_ssim_state_words": (i32, []),
+    "otvae_ms_ssim_pyramid": (i64, [i32, i32, i32, i32, i32, i32]),
+    "otvae_ms_ssim_ws": (i64, [i32, i32, i32, i32, i32, i32, i32]),
+    "otvae_ms_ssim_accum": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, i32, pf64, i32, vp, vp,
+                                  vp, vp, vp, vp, vp]),
+    "otvae_ms_ssim_grad_ws": (i64, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "otvae_ms_ssim_grad": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, pf64, pf64, f64, f64, i32, f64, f64, i32, vp, vp, vp,
+                                 vp, vp]),
     "otvae_poly_mmd_ws": (i64, [i32, i32, i32]),
     "otvae_poly_mmd_subsets": (i32, [vp, i64, vp, i64, i32, vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp]),
     "otvae_feature_append": (i32, [i32, vp, i32, i32, vp, i64, vp, vp]),

@@ -19,11 +19,16 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
     otvae::gaussian_blur            torchvision's gaussian_blur (GaussianBlur)   tests/test_latent_transport.py:35
     otvae::ssim_loss                SSIMLoss: the per-image SSIM values [B] and  torchmetrics' ssim, differentiable
                                     their gradient for preds and target
+    otvae::ms_ssim                  MSSSIMLoss: the per-image MS-SSIM values     torchmetrics' ms_ssim, differentiable
+                                    [B], the scale weights and the pyramid its
+                                    backward operator reads
 
-    otvae::moments_accum            FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
+    otvae::moments_accum           FrechetInceptionDistance.update's moments    metrics/fid.py:99-122   (in place, no gradient)
     otvae::sqerr_accum              PeakSignalNoiseRatio.update                  torchmetrics' psnr      (in place, no gradient)
     otvae::ssim_accum               StructuralSimilarityIndexMeasure.update      torchmetrics' ssim      (in place, no gradient)
-    otvae::feature_append           KernelInceptionDistance.update's store      torchmetrics' kid       (in place, no gradient)
+    otvae::ms_ssim_accum            MultiScaleStructuralSimilarityIndexMeasure   torchmetrics' ms_ssim   (in place, no gradient)
+                                    .update
+    otvae::feature_append           KernelInceptionDistance.update's store     torchmetrics' kid       (in place, no gradient)
     otvae::poly_mmd_subsets         KernelInceptionDistance.compute: the MMD^2   torchmetrics' kid       (no gradient)
                                     of every random subset and their mean / std
     otvae::knn_sq_radii             PrecisionRecall.compute: k-NN ball radii     no reference class      (no gradient)
@@ -50,7 +55,7 @@ from ._lib import check, ptr, stream
 __all__ = ["OPS"]
 
 OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior",
-       "soft_cross_entropy", "gaussian_blur", "sliced_w2", "mmd_prior", "ssim_loss")
+       "soft_cross_entropy", "gaussian_blur", "sliced_w2", "mmd_prior", "ssim_loss", "ms_ssim")
 _lib_def = torch.library.Library("otvae", "DEF")
 
 
@@ -1072,3 +1077,164 @@ def _ssim_loss_backward(ctx, g):
 
 torch.library.register_autograd("otvae::ssim_loss", _ssim_loss_backward, setup_context=_ssim_loss_setup)
 _refuse_second_derivative("ssim_loss_backward", "SSIM loss")
+
+
+# ------------------------------------------------------------------------------------------------ multi-scale SSIM
+MS_SSIM_NORMALIZE = {None: 0, "relu": 1, "simple": 2}   # otvae_ms_ssim_accum's normalize
+_MS_SSIM_ELEM = {torch.float32: 4, torch.float64: 8}
+
+
+def _ms_ssim_check(name: str, preds: Tensor, target: Tensor, win_h, win_w, betas, max_taps: int):
+    """the refusals every multi-scale entry shares, before any kernel; returns (lib, b, c, h, w, kh, kw, scales)"""
+    lib = _lib.load()
+    _lib.require_cuda(preds, "preds")
+    _lib.require_cuda(target, "target")
+    if preds.dim() != 4 or preds.shape != target.shape:
+        raise ValueError(f"{name} takes two [B, C, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
+    if preds.dtype not in _MS_SSIM_ELEM or target.dtype != preds.dtype:
+        raise ValueError(f"{name} takes two float32 or two float64 tensors, got {preds.dtype} and {target.dtype}")
+    if not (preds.is_contiguous() and target.is_contiguous()):
+        raise ValueError(f"{name}: preds and target must be NCHW-contiguous")
+    b, c, h, w = preds.shape
+    kh, kw, scales = len(win_h), len(win_w), len(betas)
+    if kh % 2 == 0 or kw % 2 == 0 or scales < 1:
+        raise ValueError(f"{name}: a {kh} x {kw} window must be odd, and betas must not be empty")
+    if kh > max_taps or kw > max_taps or scales > 8:
+        raise NotImplementedError(f"{name}: {scales} scales of a {kh} x {kw} window are beyond the kernel's envelope ({max_taps} taps per "
+                                  "axis, 8 scales)")
+    if (h >> (scales - 1)) < kh or (w >> (scales - 1)) < kw:
+        raise ValueError(f"{name}: {h} x {w} images are too small for {scales} scales of a {kh} x {kw} window: every scale must hold one "
+                         f"window, so the smallest admissible size is {kh << (scales - 1)} x {kw << (scales - 1)}")
+    return lib, b, c, h, w, kh, kw, scales
+
+
+def _ms_ssim_run(lib, preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, betas, normalize, per_image, weights, pyramid,
+                 state):
+    b, c, h, w = preds.shape
+    kh, kw, scales = len(win_h), len(win_w), len(betas)
+    nbytes = lib.otvae_ms_ssim_ws(b, c, h, w, kh, kw, scales)
+    if nbytes < 0:
+        raise NotImplementedError(f"ms_ssim: {tuple(preds.shape)} with {scales} scales of a {kh} x {kw} window is beyond the kernel's envelope")
+    ws = torch.empty(nbytes, device=preds.device, dtype=torch.uint8)
+    check(lib.otvae_ms_ssim_accum(0 if preds.dtype == torch.float32 else 1, ptr(preds), ptr(target), b, c, h, w, kh, kw,
+                                  (C.c_double * kh)(*win_h), (C.c_double * kw)(*win_w), float(k1), float(k2), int(range_mode),
+                                  float(range_lo), float(range_hi), scales, (C.c_double * scales)(*betas), int(normalize), ptr(per_image),
+                                  ptr(weights), ptr(pyramid[0]) if scales > 1 else None, ptr(pyramid[1]) if scales > 1 else None,
+                                  ptr(state), ptr(ws), stream()), "otvae_ms_ssim_accum")
+
+
+def _ms_ssim_pyramid(lib, preds: Tensor, scales: int) -> Tensor:
+    """[2][elements]: scales 1 .. S - 1 of preds, then of target"""
+    b, c, h, w = preds.shape
+    nbytes = max(0, lib.otvae_ms_ssim_pyramid(0 if preds.dtype == torch.float32 else 1, b, c, h, w, scales)) if b and c else 0
+    return torch.empty((2, nbytes // _MS_SSIM_ELEM[preds.dtype]), dtype=preds.dtype, device=preds.device)
+
+
+def _ms_ssim_accum(preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: float, range_mode: int, range_lo: float, range_hi: float,
+                   betas, normalize: int, state: Tensor, per_image: Optional[Tensor]) -> None:
+    lib, b, c, _, _, _, _, scales = _ms_ssim_check("ms_ssim_accum", preds, target, win_h, win_w, betas, 31)
+    words = lib.otvae_ms_ssim_state_words()
+    if state.dtype != torch.float64 or state.numel() != words or not state.is_contiguous():
+        raise ValueError(f"ms_ssim_accum: state must be {words} contiguous float64 words")
+    if per_image is not None and (per_image.dtype != torch.float64 or tuple(per_image.shape) != (b,) or not per_image.is_contiguous()):
+        raise ValueError(f"ms_ssim_accum: per_image must be a contiguous float64 tensor of shape ({b},)")
+    if range_mode not in (SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP, SSIM_RANGE_BATCH) or normalize not in (0, 1, 2):
+        raise ValueError(f"ms_ssim_accum: range_mode must be 0, 1 or 2 and normalize 0, 1 or 2, got {range_mode} and {normalize}")
+    if b == 0 or c == 0:
+        return
+    _ms_ssim_run(lib, preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, betas, normalize, per_image, None,
+                 _ms_ssim_pyramid(lib, preds, scales), state)
+
+
+_define("ms_ssim_accum", "(Tensor preds, Tensor target, float[] win_h, float[] win_w, float k1, float k2, int range_mode, float range_lo, "
+        "float range_hi, float[] betas, int normalize, Tensor(a!) state, Tensor(b!)? per_image) -> ()", _ms_ssim_accum,
+        lambda preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, betas, normalize, state, per_image: None)
+
+
+def _ms_ssim_loss_check(name, preds, target, win_h, win_w, betas, range_mode, normalize):
+    out = _ms_ssim_check(name, preds, target, win_h, win_w, betas, 15)
+    if range_mode not in (SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP):
+        raise ValueError(f"{name}: range_mode must be 0 (fixed) or 1 (clamp), got {range_mode}: a range taken from the batch depends on "
+                         "the data, and a loss needs a fixed scale")
+    if normalize not in (0, 1, 2):
+        raise ValueError(f"{name}: normalize must be 0 (none), 1 (relu) or 2 (simple), got {normalize}")
+    return out
+
+
+def _ms_ssim_fwd(preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: float, range_mode: int, range_lo: float, range_hi: float,
+                 betas, normalize: int):
+    """(msssim [B] float64, w [S][B] float64, the pyramid [2][elements] of both images): what the backward operator needs"""
+    lib, b, c, _, _, _, _, scales = _ms_ssim_loss_check("ms_ssim", preds, target, win_h, win_w, betas, range_mode, normalize)
+    per_image = torch.empty(b, dtype=torch.float64, device=preds.device)
+    weights = torch.empty((scales, b), dtype=torch.float64, device=preds.device)
+    pyramid = _ms_ssim_pyramid(lib, preds, scales)
+    if b == 0 or c == 0:
+        return per_image, weights, pyramid
+    state = torch.empty(lib.otvae_ms_ssim_state_words(), dtype=torch.float64, device=preds.device)   # written, never read
+    _ms_ssim_run(lib, preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, betas, normalize, per_image, weights, pyramid,
+                 state)
+    return per_image, weights, pyramid
+
+
+def _ms_ssim_fwd_fake(preds, target, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, betas, normalize):
+    b, c, h, w = preds.shape
+    n = sum(b * c * (h >> s) * (w >> s) for s in range(1, len(betas)))
+    return (preds.new_empty((b,), dtype=torch.float64), preds.new_empty((len(betas), b), dtype=torch.float64), preds.new_empty((2, n)))
+
+
+def _ms_ssim_bwd(g: Tensor, weights: Tensor, pyramid: Tensor, preds: Tensor, target: Tensor, swap: bool, win_h, win_w, k1: float,
+                 k2: float, range_mode: int, range_lo: float, range_hi: float, betas, normalize: int) -> Tensor:
+    """d sum_b g[b] msssim_b / d preds; ``swap``: ``preds`` / ``target`` arrive exchanged and so do the pyramid's two rows (the gradient for
+    the forward's ``target``: every term is symmetric)"""
+    lib, b, c, h, w, kh, kw, scales = _ms_ssim_loss_check("ms_ssim_backward", preds, target, win_h, win_w, betas, range_mode, normalize)
+    if tuple(g.shape) != (b,) or tuple(weights.shape) != (scales, b) or weights.dtype != torch.float64:
+        raise ValueError(f"ms_ssim_backward: the cotangent must have shape ({b},) and the weights ({scales}, {b}) in float64, got "
+                         f"{tuple(g.shape)} and {tuple(weights.shape)}")
+    grad = torch.empty(preds.shape, dtype=preds.dtype, device=preds.device)
+    if b == 0 or c == 0:
+        return grad
+    in_dtype = 0 if preds.dtype == torch.float32 else 1
+    want = lib.otvae_ms_ssim_pyramid(in_dtype, b, c, h, w, scales) // _MS_SSIM_ELEM[preds.dtype]
+    if pyramid.dtype != preds.dtype or tuple(pyramid.shape) != (2, want) or not pyramid.is_contiguous():
+        raise ValueError(f"ms_ssim_backward: the pyramid must be the forward's (2, {want}) tensor of {preds.dtype}")
+    g = g.to(torch.float64).contiguous()
+    nbytes = lib.otvae_ms_ssim_grad_ws(in_dtype, b, c, h, w, kh, kw, scales)
+    if nbytes < 0:
+        raise NotImplementedError(f"ms_ssim_backward: {tuple(preds.shape)} with {scales} scales of a {kh} x {kw} window is beyond the "
+                                  "gradient kernel's envelope")
+    ws = torch.empty(nbytes, device=preds.device, dtype=torch.uint8) if nbytes else None
+    pyr_p, pyr_t = (pyramid[1], pyramid[0]) if swap else (pyramid[0], pyramid[1])
+    check(lib.otvae_ms_ssim_grad(in_dtype, ptr(preds), ptr(target), ptr(pyr_p) if scales > 1 else None, ptr(pyr_t) if scales > 1 else None,
+                                 b, c, h, w, kh, kw, (C.c_double * kh)(*win_h), (C.c_double * kw)(*win_w), float(k1), float(k2),
+                                 int(range_mode), float(range_lo), float(range_hi), scales, ptr(g), ptr(weights.contiguous()), ptr(grad),
+                                 ptr(ws), stream()), "otvae_ms_ssim_grad")
+    return grad
+
+
+_define("ms_ssim", "(Tensor preds, Tensor target, float[] win_h, float[] win_w, float k1, float k2, int range_mode, float range_lo, "
+        "float range_hi, float[] betas, int normalize) -> (Tensor, Tensor, Tensor)", _ms_ssim_fwd, _ms_ssim_fwd_fake)
+_define("ms_ssim_backward", "(Tensor g, Tensor weights, Tensor pyramid, Tensor preds, Tensor target, bool swap, float[] win_h, "
+        "float[] win_w, float k1, float k2, int range_mode, float range_lo, float range_hi, float[] betas, int normalize) -> Tensor",
+        _ms_ssim_bwd,
+        lambda g, weights, pyramid, preds, target, swap, win_h, win_w, k1, k2, range_mode, range_lo, range_hi, betas, normalize:
+        preds.new_empty(preds.shape))
+
+
+def _ms_ssim_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0], inputs[1], output[1], output[2])
+    ctx.cfg = inputs[2:]
+    ctx.set_materialize_grads(False)   # w and the pyramid never carry a gradient
+
+
+def _ms_ssim_backward(ctx, g, _gw, _gpyr):
+    if g is None:
+        return (None,) * 11
+    preds, target, weights, pyramid = ctx.saved_tensors
+    need_p, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    gp = torch.ops.otvae.ms_ssim_backward(g, weights, pyramid, preds, target, False, *ctx.cfg) if need_p else None
+    gt = torch.ops.otvae.ms_ssim_backward(g, weights, pyramid, target, preds, True, *ctx.cfg) if need_t else None
+    return (gp, gt) + (None,) * 9
+
+
+torch.library.register_autograd("otvae::ms_ssim", _ms_ssim_backward, setup_context=_ms_ssim_setup)
+_refuse_second_derivative("ms_ssim_backward", "MS-SSIM loss")
