@@ -694,7 +694,7 @@ int64_t otvae_ssim_grad_ws(int B, int C, int H, int W, int kh, int kw); /* bytes
 int otvae_ssim_grad(int in_dtype, const void* preds, const void* target, int B, int C, int H, int W, int kh, int kw, const double* wh,
                     const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi, const double* g,
                     void* grad_preds, void* ws, void* stream);
-/* MultiScaleStructuralSimilarityIndexMeasure's accumulation (csrc/ms_ssim.hip; metrics/ms_ssim.py): otvae_ssim_accum's map, window,
+/* MultiScaleStructuralSimilarityIndexMeasure's accumulation (csrc/ssim.hip; metrics/ms_ssim.py): otvae_ssim_accum's map, window,
  * in_dtype, range_mode and state layout, over S scales.  With p_0 = preds, t_0 = target and scale s on [B][C][H >> s][W >> s],
  *   cs   = (2 s_pt + c2) / (s_pp + s_tt + c2),   ssim = (2 mu_p mu_t + c1) / (mu_p^2 + mu_t^2 + c1) * cs    at every valid position,
  *   v_s[b] = the mean over C and all positions of cs for s < S - 1, of ssim for s = S - 1,
@@ -722,7 +722,7 @@ int otvae_ms_ssim_accum(int in_dtype, const void* preds, const void* target, int
                         const double* wh, const double* ww, double k1, double k2, int range_mode, double range_lo, double range_hi,
                         int S, const double* betas, int normalize, double* per_image, double* w, void* pyr_preds, void* pyr_target,
                         double* state, void* ws, void* stream);
-/* The gradient of otvae_ms_ssim_accum's per-image values (csrc/ms_ssim.hip; losses.py's MSSSIMLoss): with an upstream cotangent g[b]
+/* The gradient of otvae_ms_ssim_accum's per-image values (csrc/ssim_grad.hip; losses.py's MSSSIMLoss): with an upstream cotangent g[b]
  * (DEVICE array, fp64) on msssim_b, the weights w [S][B] and the pyramids that call left, and n_s = C (H_s - kh + 1) (W_s - kw + 1),
  *   d/dp_s[q] = own_s(q) + 1/4 d/dp_{s+1}[q >> 1]   (no second term at the last scale, nor under a dropped odd row / column),
  *   own_s(q) = alpha(q) + 2 p_q beta(q) + t_q gamma(q),   alpha, beta, gamma = W^T[(g_b w_s[b] / n_s) (a, b, c)]

@@ -5,9 +5,9 @@ The forward is the metric's kernel (``otvae_ssim_accum``, ``csrc/ssim.hip``: the
 ``metrics.structural_similarity``), the backward one launch of ``otvae_ssim_grad`` (``csrc/ssim_grad.hip``) per image that wants a
 gradient; both behind ``torch.ops.otvae.ssim_loss``.  Options, their checks and the windows are ``metrics.ssim._Options``.
 
-``MSSSIMLoss`` / ``ms_ssim_loss``: ``1 - MS-SSIM`` per image, the same way: the forward is ``otvae_ms_ssim_accum`` (``csrc/ms_ssim.hip``: the
+``MSSSIMLoss`` / ``ms_ssim_loss``: ``1 - MS-SSIM`` per image, the same way: the forward is ``otvae_ms_ssim_accum`` (``csrc/ssim.hip``: the
 bits of ``metrics.multiscale_structural_similarity``), which keeps the pooled pyramid and the scale weights, the backward one launch
-of ``otvae_ms_ssim_grad`` per scale, coarsest first; both behind ``torch.ops.otvae.ms_ssim``.  ``losses.__all__`` is the pair of names the
+of ``otvae_ms_ssim_grad`` (``csrc/ssim_grad.hip``, the SSIM gradient's tile kernel) per scale, coarsest first; both behind ``torch.ops.otvae.ms_ssim``.  ``losses.__all__`` is the pair of names the
 module began with (``tests/test_ssim_loss_host.py`` holds it to exactly that); the package exports the two new names itself."""
 from typing import Optional, Tuple
 

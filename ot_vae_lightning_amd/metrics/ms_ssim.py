@@ -1,5 +1,5 @@
 """``MultiScaleStructuralSimilarityIndexMeasure`` and ``multiscale_structural_similarity``: torchmetrics' MS-SSIM over everything seen
-since ``reset()``, by ``otvae_ms_ssim_accum`` (``csrc/ms_ssim.hip``): one launch per scale that reads the scale's pair once, reduces the
+since ``reset()``, by ``otvae_ms_ssim_accum`` (``csrc/ssim.hip``): one launch per scale that reads the scale's pair once, reduces the
 contrast term and the full map and writes the 2 x 2 pooled pair of the next scale, then one fold over all scales.
 
 As for SSIM, only the positions whose window lies inside the image are evaluated (what torchmetrics keeps after its reflect padding

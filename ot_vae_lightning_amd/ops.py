@@ -959,16 +959,22 @@ _define("manifold_counts", "(Tensor real, Tensor r2_real, Tensor fake, Tensor r2
 SSIM_RANGE_FIXED, SSIM_RANGE_CLAMP, SSIM_RANGE_BATCH = 0, 1, 2   # otvae_ssim_accum's range_mode
 
 
-def _ssim_accum(preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: float, range_mode: int, range_lo: float, range_hi: float,
-                state: Tensor, per_image: Optional[Tensor]) -> None:
-    """``win_h`` / ``win_w``: the window's weights per axis, float64 values of the host (they travel in the kernel's argument block)"""
+def _ssim_pair_check(name: str, preds: Tensor, target: Tensor):
+    """what every SSIM entry asks of its image pair first: on the device, [B, C, H, W] of one shape, one float dtype; returns lib"""
     lib = _lib.load()
     _lib.require_cuda(preds, "preds")
     _lib.require_cuda(target, "target")
     if preds.dim() != 4 or preds.shape != target.shape:
-        raise ValueError(f"ssim_accum takes two [B, C, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
+        raise ValueError(f"{name} takes two [B, C, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
     if preds.dtype not in (torch.float32, torch.float64) or target.dtype != preds.dtype:
-        raise ValueError(f"ssim_accum takes two float32 or two float64 tensors, got {preds.dtype} and {target.dtype}")
+        raise ValueError(f"{name} takes two float32 or two float64 tensors, got {preds.dtype} and {target.dtype}")
+    return lib
+
+
+def _ssim_accum(preds: Tensor, target: Tensor, win_h, win_w, k1: float, k2: float, range_mode: int, range_lo: float, range_hi: float,
+                state: Tensor, per_image: Optional[Tensor]) -> None:
+    """``win_h`` / ``win_w``: the window's weights per axis, float64 values of the host (they travel in the kernel's argument block)"""
+    lib = _ssim_pair_check("ssim_accum", preds, target)
     if not (preds.is_contiguous() and target.is_contiguous()):
         raise ValueError("ssim_accum: preds and target must be NCHW-contiguous")
     b, c, h, w = preds.shape
@@ -1004,13 +1010,7 @@ _define("ssim_accum", "(Tensor preds, Tensor target, float[] win_h, float[] win_
 # ------------------------------------------------------------------------------------------------ SSIM as a loss
 def _ssim_loss_check(name: str, preds: Tensor, target: Tensor, win_h, win_w, range_mode: int):
     """the refusals the forward and the backward share, before any kernel; returns (lib, b, c, h, w, kh, kw)"""
-    lib = _lib.load()
-    _lib.require_cuda(preds, "preds")
-    _lib.require_cuda(target, "target")
-    if preds.dim() != 4 or preds.shape != target.shape:
-        raise ValueError(f"{name} takes two [B, C, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
-    if preds.dtype not in (torch.float32, torch.float64) or target.dtype != preds.dtype:
-        raise ValueError(f"{name} takes two float32 or two float64 tensors, got {preds.dtype} and {target.dtype}")
+    lib = _ssim_pair_check(name, preds, target)
     b, c, h, w = preds.shape
     kh, kw = len(win_h), len(win_w)
     if kh % 2 == 0 or kw % 2 == 0 or h < kh or w < kw:
@@ -1086,13 +1086,7 @@ _MS_SSIM_ELEM = {torch.float32: 4, torch.float64: 8}
 
 def _ms_ssim_check(name: str, preds: Tensor, target: Tensor, win_h, win_w, betas, max_taps: int):
     """the refusals every multi-scale entry shares, before any kernel; returns (lib, b, c, h, w, kh, kw, scales)"""
-    lib = _lib.load()
-    _lib.require_cuda(preds, "preds")
-    _lib.require_cuda(target, "target")
-    if preds.dim() != 4 or preds.shape != target.shape:
-        raise ValueError(f"{name} takes two [B, C, H, W] tensors of one shape, got {tuple(preds.shape)} and {tuple(target.shape)}")
-    if preds.dtype not in _MS_SSIM_ELEM or target.dtype != preds.dtype:
-        raise ValueError(f"{name} takes two float32 or two float64 tensors, got {preds.dtype} and {target.dtype}")
+    lib = _ssim_pair_check(name, preds, target)
     if not (preds.is_contiguous() and target.is_contiguous()):
         raise ValueError(f"{name}: preds and target must be NCHW-contiguous")
     b, c, h, w = preds.shape

@@ -1,4 +1,4 @@
-"""GPU: ``MultiScaleStructuralSimilarityIndexMeasure`` / ``multiscale_structural_similarity`` (``csrc/ms_ssim.hip``) against the
+"""GPU: ``MultiScaleStructuralSimilarityIndexMeasure`` / ``multiscale_structural_similarity`` (``csrc/ssim.hip``) against the
 definition (``tests/ms_ssim_definition.py``) evaluated in float64 on the CPU.
 
 Truth and bound, per image, under the evidence rule of ``tests/test_gpu_ssim.py``:

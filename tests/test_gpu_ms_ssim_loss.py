@@ -1,4 +1,4 @@
-"""GPU: ``MSSSIMLoss`` / ``ms_ssim_loss`` / ``torch.ops.otvae.ms_ssim`` (``csrc/ms_ssim.hip``) against float64 autograd of the definition
+"""GPU: ``MSSSIMLoss`` / ``ms_ssim_loss`` / ``torch.ops.otvae.ms_ssim`` (``csrc/ssim.hip``, ``csrc/ssim_grad.hip``) against float64 autograd of the definition
 (``tests/ms_ssim_definition.py``), evaluated on the CPU.
 
 Truth and bound.  The float64 autograd gradient of ``sum_b g_b (1 - msssim_b)`` is the truth, the float32 autograd gradient of the same
@@ -189,6 +189,26 @@ def test_forward_bits_and_determinism(A, dtype):
 
 
 # 7 ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("window", [dict(), dict(gaussian=False, kernel_size=(3, 5))], ids=["11x11", "3x5"])
+def test_one_scale_gradient_has_the_bits_of_the_ssim_gradient(A, window, dtype):
+    """One scale, ``betas = (1.0,)``, no normalisation: msssim_b = pow(v, 1) and the fold's weight is 1.0 exactly, so the gradient kernel
+    -- one body, ``ssg_tile_kernel`` of ``csrc/ssim_grad.hip``, for both losses -- does the SSIM gradient's arithmetic.  (The forward values
+    agree to 1e-12 only: the two folds sum in different orders, ``test_gpu_ms_ssim.py::test_one_scale_is_ssim``.)"""
+    p, t = pair_of((2, 2, 19, 37), 1.0, seed=97, dtype=dtype)
+    g = _cotangent(2, 97).to(dtype).cuda()
+    grads = []
+    for loss_fn, extra in ((A.ms_ssim_loss, dict(betas=(1.0,), normalize=None)), (A.ssim_loss, {})):
+        pc = p.cuda().requires_grad_(True)
+        loss = loss_fn(pc, t.cuda(), data_range=1.0, reduction="none", **option_kwargs(window), **extra)
+        assert bool(torch.isfinite(loss).all()) and bool((loss != 1.0).all())   # a finite non-zero msssim_b: the weight is 1.0
+        loss.backward(g)
+        grads.append(pc.grad)
+    assert bool((grads[1] != 0).any())
+    assert torch.equal(grads[0], grads[1]), f"{int((grads[0] != grads[1]).sum())} elements differ"
+
+
+# 8 ------------------------------------------------------------------------------------------------------------------------------
 def test_refusals(A):
     x = torch.rand(2, 1, 32, 32)
     with pytest.raises(RuntimeError):
@@ -212,7 +232,7 @@ def test_refusals(A):
         torch.ops.otvae.ms_ssim(xc, xc.double(), o.window[0], o.window[1], o.k1, o.k2, 0, 0.0, 1.0, o.betas, 1)
 
 
-# 8 ------------------------------------------------------------------------------------------------------------------------------
+# 9 ------------------------------------------------------------------------------------------------------------------------------
 B, IMG = 8, (1, 32, 32)
 
 

@@ -3,7 +3,7 @@
     [256, 3, 64, 64]    3 betas, sigma 1.0 (7 taps)         the reconstruction-loss shape
     [16, 3, 256, 256]   the default 5 betas, 11 x 11 window  the validation shape
 
-    update        MultiScaleStructuralSimilarityIndexMeasure.update          (csrc/ms_ssim.hip: one launch per scale + the fold)
+    update        MultiScaleStructuralSimilarityIndexMeasure.update          (csrc/ssim.hip: one launch per scale + the fold)
     loss          MSSSIMLoss(preds, target).backward()                        (that forward, then one gradient launch per scale)
     composition   per scale: stack the five maps, grouped conv2d over the valid positions, the maps element-wise, mean per image,
                   two avg_pool2d; the product of powers; for the loss its .backward()   (what a user would write without the kernels)
