@@ -276,8 +276,6 @@ __global__ __launch_bounds__(ARD_THREADS) void ar_layer_step_kernel(
     ard_layernorm(xs, ldx, D, g2, be2, eps2, y, row0, B);
 }
 
-static bool g_ard_lds_set = false;
-
 extern "C" int otvae_ar_layer_step(const float* x, int B, int D, int H, int F, int pos, int Tmax, const float* w_in, const float* b_in,
                                    const float* w_out, const float* b_out, const float* ln1_g, const float* ln1_b, float eps1,
                                    const float* w1, const float* b1, const float* w2, const float* b2, const float* ln2_g,
@@ -297,14 +295,9 @@ extern "C" int otvae_ar_layer_step(const float* x, int B, int D, int H, int F, i
         return OTVAE_EUNSUPPORTED;
     }
     const size_t lds = (size_t)ARD_ROWS * (4 * D + 2 * ARD_PAD) * sizeof(float);
-    if (lds > 65536 && !g_ard_lds_set) {
-        if (hipFuncSetAttribute((const void*)ar_layer_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)ARD_ROWS * (4 * ARD_MAX_D + 2 * ARD_PAD) * sizeof(float))) != hipSuccess) {
-            otvae_set_error("otvae_ar_layer_step: cannot raise the dynamic LDS limit");
-            return OTVAE_ELAUNCH;
-        }
-        g_ard_lds_set = true;
-    }
+    if (int rc = otvae_lds_grant<&ar_layer_step_kernel>("otvae_ar_layer_step", lds,
+                                                        (size_t)ARD_ROWS * (4 * ARD_MAX_D + 2 * ARD_PAD) * sizeof(float)))
+        return rc;
     ar_layer_step_kernel<<<cdiv(B, ARD_ROWS), ARD_THREADS, lds, (hipStream_t)stream>>>(x, B, D, H, F, pos, Tmax, w_in, b_in, w_out, b_out, ln1_g,
                                                                                         ln1_b, eps1, w1, b1, w2, b2, ln2_g, ln2_b, eps2, kcache,
                                                                                         vcache, y);

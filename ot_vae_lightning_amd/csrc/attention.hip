@@ -1314,20 +1314,7 @@ extern "C" int otvae_attn_fwd_scaled(const float* qkv, int N, int T, int H, int 
 }
 
 // ---- the fused AttentionBlock forward (attn_stage_fwd_kernel)
-#define ATTN_STAGE_LDS_FLOATS 24576  // 96 KiB of the CU's 160: above 64 KiB a kernel has to be told (stage_lds_ok), two workgroups still share a CU
-template <auto Kernel>
-static int stage_lds_ok(size_t lds) {
-    static size_t granted = 64 * 1024;  // per kernel instantiation
-    if (lds <= granted) return OTVAE_OK;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             ATTN_STAGE_LDS_FLOATS * sizeof(float));
-    if (e != hipSuccess) {
-        otvae_set_error("otvae_attn_stage_fwd: %zu bytes of LDS refused: %s", lds, hipGetErrorString(e));
-        return OTVAE_ELAUNCH;
-    }
-    granted = ATTN_STAGE_LDS_FLOATS * sizeof(float);
-    return OTVAE_OK;
-}
+#define ATTN_STAGE_LDS_FLOATS 24576  // 96 KiB of the CU's 160: above 64 KiB a kernel has to be told (otvae_lds_grant), two workgroups still share a CU
 static inline bool attn_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // Launch shape, or OTVAE_EUNSUPPORTED when the stage has to run as three launches: a block must own whole images (spb % H == 0), the token
 // GEMMs want T % 4 == 0, the per-column statistics a power-of-two width <= 64.
@@ -1441,22 +1428,29 @@ static int attn_stage_fwd_impl(const float* x, const float* scale, const float* 
                   "otvae_attn_stage_fwd: qkv / y / residual must be 8-byte aligned");
     const AttnStage sg = {x, scale, shift, wqkv, wproj, residual, qkv, y, stat_partial, fold};
     hipStream_t st = (hipStream_t)stream;
-#define STAGE_K(CC)                                                                                                        \
-    do {                                                                                                                   \
-        if (qpt == 4) {                                                                                                    \
-            if constexpr (CC <= 2) {                                                                                       \
-                if (aux) { rc = stage_lds_ok<&attn_stage_fwd_kernel<CC, 4, true>>(lds); if (rc) return rc; (attn_stage_fwd_kernel<CC, 4, true>)<<<grid, nthr, lds, st>>>(sg, N, T, H, spb, out, lse, aux, qk_scale); } \
-                else { rc = stage_lds_ok<&attn_stage_fwd_kernel<CC, 4, false>>(lds); if (rc) return rc; (attn_stage_fwd_kernel<CC, 4, false>)<<<grid, nthr, lds, st>>>(sg, N, T, H, spb, out, lse, nullptr, qk_scale); } \
-            } else if constexpr (CC <= 4) { rc = stage_lds_ok<&attn_stage_fwd_kernel<CC, 4, false>>(lds); if (rc) return rc; (attn_stage_fwd_kernel<CC, 4, false>)<<<grid, nthr, lds, st>>>(sg, N, T, H, spb, out, lse, nullptr, qk_scale); } \
-        } else {                                                                                                           \
-            if constexpr (CC <= 2) {                                                                                       \
-                if (aux) { rc = stage_lds_ok<&attn_stage_fwd_kernel<CC, 1, true>>(lds); if (rc) return rc; (attn_stage_fwd_kernel<CC, 1, true>)<<<grid, nthr, lds, st>>>(sg, N, T, H, spb, out, lse, aux, qk_scale); } \
-                else { rc = stage_lds_ok<&attn_stage_fwd_kernel<CC, 1, false>>(lds); if (rc) return rc; (attn_stage_fwd_kernel<CC, 1, false>)<<<grid, nthr, lds, st>>>(sg, N, T, H, spb, out, lse, nullptr, qk_scale); } \
-            } else { rc = stage_lds_ok<&attn_stage_fwd_kernel<CC, 1, false>>(lds); if (rc) return rc; (attn_stage_fwd_kernel<CC, 1, false>)<<<grid, nthr, lds, st>>>(sg, N, T, H, spb, out, lse, nullptr, qk_scale); } \
-        }                                                                                                                  \
+#define STAGE_FK(K_, AUX_)                                                                                              \
+    {                                                                                                                   \
+        rc = otvae_lds_grant<&K_>("otvae_attn_stage_fwd", lds, ATTN_STAGE_LDS_FLOATS * sizeof(float));                  \
+        if (rc) return rc;                                                                                              \
+        K_<<<grid, nthr, lds, st>>>(sg, N, T, H, spb, out, lse, AUX_, qk_scale);                                        \
+    }
+#define STAGE_K(CC)                                                                                                     \
+    do {                                                                                                                \
+        if (qpt == 4) {                                                                                                 \
+            if constexpr (CC <= 2) {                                                                                    \
+                if (aux) STAGE_FK((attn_stage_fwd_kernel<CC, 4, true>), aux)                                            \
+                else STAGE_FK((attn_stage_fwd_kernel<CC, 4, false>), nullptr)                                           \
+            } else if constexpr (CC <= 4) STAGE_FK((attn_stage_fwd_kernel<CC, 4, false>), nullptr)                      \
+        } else {                                                                                                        \
+            if constexpr (CC <= 2) {                                                                                    \
+                if (aux) STAGE_FK((attn_stage_fwd_kernel<CC, 1, true>), aux)                                            \
+                else STAGE_FK((attn_stage_fwd_kernel<CC, 1, false>), nullptr)                                           \
+            } else STAGE_FK((attn_stage_fwd_kernel<CC, 1, false>), nullptr)                                             \
+        }                                                                                                               \
     } while (0)
     ATTN_C_SWITCH(C, STAGE_K)
 #undef STAGE_K
+#undef STAGE_FK
     OTVAE_CHECK_LAUNCH("otvae_attn_stage_fwd");
     return OTVAE_OK;
 }
@@ -1507,7 +1501,7 @@ static int attn_stage_bwd_impl(const float* gy, const float* wproj, const float*
     hipStream_t st = (hipStream_t)stream;
 #define STAGE_BK(K_)                                                                                  \
     {                                                                                                 \
-        rc = stage_lds_ok<&K_>(lds);                                                                  \
+        rc = otvae_lds_grant<&K_>("otvae_attn_stage_bwd", lds, ATTN_STAGE_LDS_FLOATS * sizeof(float)); \
         if (rc) return rc;                                                                            \
         K_<<<grid, nthr, lds, st>>>(sg, qkv, out, lse, aux, N, T, H, spb, gqkv, qk_scale);            \
     }

@@ -3,7 +3,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
-#include "../../include/otvae.h"
+#include "common.h"
 
 static thread_local char g_err[512] = "";
 
@@ -12,6 +12,22 @@ void otvae_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+
+int otvae_current_device() {
+    int dev = -1;
+    return hipGetDevice(&dev) == hipSuccess ? dev : -1;
+}
+
+int otvae_cu_count() {
+    static std::atomic<int> tab[OTVAE_MAX_DEVICES];  // 0: not asked yet
+    const int dev = otvae_current_device();
+    std::atomic<int>* rec = dev >= 0 && dev < OTVAE_MAX_DEVICES ? &tab[dev] : nullptr;
+    int v = rec ? rec->load(std::memory_order_relaxed) : 0;
+    if (v > 0) return v;
+    if (dev < 0 || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 1;
+    if (rec) rec->store(v, std::memory_order_relaxed);
+    return v;
 }
 
 extern "C" const char* otvae_last_error(void) { return g_err; }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <atomic>
 #include "../../include/otvae.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -28,6 +29,31 @@ void otvae_set_error(const char* fmt, ...);
             return OTVAE_ELAUNCH;                                                   \
         }                                                                           \
     } while (0)
+
+// ---- per-device host state: what the host remembers about a device is indexed by the device it was learnt on ------------
+#define OTVAE_MAX_DEVICES 16
+int otvae_current_device();  // the calling thread's current HIP device, -1 when hipGetDevice fails
+int otvae_cu_count();        // CUs of the current device, asked once per device (every call beyond the table); 1 when the query fails
+
+// A launch with more than 64 KiB of dynamic LDS has to be granted first, and HIP keeps that attribute per function AND per device.
+// need: bytes this launch asks for; most: what to request when a grant is needed (the kernel's widest supported shape).
+// Users: conv_tile.hip (one-job and pair kernels), conv_wtile.hip, attention.hip (stage forward / backward), mmd.hip, mvn.hip,
+// ar_decode.hip, eigh_onesided.hip (hj_sweep_kernel, hjg_round_kernel), gaussian_ot.hip (eigh_kernel).
+template <auto Kernel>
+static int otvae_lds_grant(const char* who, size_t need, size_t most) {
+    if (need <= 64 * 1024) return OTVAE_OK;
+    static std::atomic<size_t> have[OTVAE_MAX_DEVICES];  // per instantiation; relaxed: setting the same attribute twice is harmless
+    const int dev = otvae_current_device();
+    std::atomic<size_t>* rec = dev >= 0 && dev < OTVAE_MAX_DEVICES ? &have[dev] : nullptr;  // outside the table: ask every time
+    if (rec && rec->load(std::memory_order_relaxed) >= need) return OTVAE_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
+    if (e != hipSuccess) {
+        otvae_set_error("%s: %zu bytes of dynamic LDS refused: %s", who, need, hipGetErrorString(e));
+        return OTVAE_ELAUNCH;
+    }
+    if (rec) rec->store(most, std::memory_order_relaxed);
+    return OTVAE_OK;
+}
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int imin(int a, int b) { return a < b ? a : b; }

@@ -833,6 +833,7 @@ static int conv_fwd_ex(const otvae_conv_geom* gg, const float* x, const float* s
                               (!residual || aligned16(residual)) && (!scale || (aligned16(scale) && aligned16(shift))),
                           "otvae_conv_fwd: tensors of a layer with channel counts %% 4 == 0 must be 16-byte aligned");
             rc = conv_tile_fwd(pl, tg, sm, (hipStream_t)stream, x, scale, shift, relu, wT, bias, residual, y, stat_dst, fold);
+            if (rc == OTVAE_ELAUNCH) return rc;
             OTVAE_REQUIRE(rc == 0, "otvae_conv_fwd: no image-tile kernel for nt=%d rbw=%d", pl.nt, pl.rbw);
             OTVAE_CHECK_LAUNCH("otvae_conv_fwd(tile)");
             return OTVAE_OK;
@@ -970,6 +971,7 @@ static int conv_bwd_data_ex(const otvae_conv_geom* gg, const float* gy, const fl
                               (!scale || (aligned16(scale) && aligned16(shift))) && (!mean || (aligned16(mean) && aligned16(invstd))),
                           "otvae_conv_bwd_data: tensors of a layer with channel counts %% 4 == 0 must be 16-byte aligned");
             rc = conv_tile_dgrad(pl, tg, sm, (hipStream_t)stream, gy, wD, x, scale, shift, relu, mean, invstd, gv, bn_partial);
+            if (rc == OTVAE_ELAUNCH) return rc;
             OTVAE_REQUIRE(rc == 0, "otvae_conv_bwd_data: no image-tile kernel for nt=%d rbw=%d", pl.nt, pl.rbw);
             OTVAE_CHECK_LAUNCH("otvae_conv_bwd_data(tile)");
             return OTVAE_OK;
@@ -1388,7 +1390,8 @@ extern "C" int otvae_conv_bwd_weight(const otvae_conv_geom* gg, const float* x, 
         if (conv_wtile_plan(g, has_bias, wp, nbk, sm)) {
             OTVAE_REQUIRE(!wp.vec4 || (aligned16(x) && (!scale || (aligned16(scale) && aligned16(shift)))),
                           "otvae_conv_bwd_weight: x / scale / shift of a layer with Cs %% 4 == 0 must be 16-byte aligned");
-            conv_wtile(wp, nbk, sm, st, x, scale, shift, relu, gy, partial);
+            rc = conv_wtile(wp, nbk, sm, st, x, scale, shift, relu, gy, partial);
+            if (rc) return rc;
             OTVAE_CHECK_LAUNCH("otvae_conv_bwd_weight(tile)");
             if (defer_reduce) return OTVAE_OK;
             P = conv_wtile_nparts(nbk);
@@ -1805,7 +1808,7 @@ static int launch_pair_ordered(const PairJob& p, const PairJob& q, hipStream_t s
 // index in them is job-local, so a caller that hands the skip in first gets the same launch with the jobs exchanged.
 static int launch_pair(const PairJob& p, const PairJob& q, hipStream_t st) {
     const int rc = launch_pair_ordered(p, q, st);
-    return rc == 0 ? 0 : launch_pair_ordered(q, p, st);
+    return rc == -1 ? launch_pair_ordered(q, p, st) : rc;  // (OTVAE_ELAUNCH, a refused LDS grant, goes up as it is)
 }
 
 static int run_single_job(const otvae_conv_job& jb, void* stream) {
@@ -2003,6 +2006,7 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
                         pend.idx = -1;
                         continue;
                     }
+                    if (pr != -1) return pr;
                 }
                 rc = flush_pend();
                 if (rc) return rc;

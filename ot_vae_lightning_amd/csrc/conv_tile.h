@@ -48,6 +48,8 @@ struct TileJobArgs {
 };
 
 bool conv_tile_plan(const Geom& g, int mode, TilePlan& pl, dim3& grid, size_t& smem);
+// The three launchers return 0, -1 when no kernel is instantiated for the plan (nothing launched, no error text), or OTVAE_ELAUNCH
+// when the LDS grant was refused (otvae_lds_grant has set the error text).
 int conv_tile_fwd(const TilePlan& pl, dim3 grid, size_t smem, hipStream_t st, const float* x, const float* scale,
                   const float* shift, int relu, const float* wT, const float* bias, const float* res, float* y,
                   double* partial, const BnFold& fold = BnFold{});

@@ -262,14 +262,10 @@ static int tile_launch(const TilePlan& pl, dim3 grid, size_t smem, hipStream_t s
                        const float* shift, int relu, const float* Wg, const float* bias, const float* res, float* y,
                        const float* xin, const float* mean, const float* invstd, float* gv, double* partial,
                        const BnFold& fold = BnFold{}) {
+    const char* who = MODE == 0 ? "otvae_conv_fwd(tile)" : "otvae_conv_bwd_data(tile)";
 #define TL(N_, R_)                                                                                                    \
     do {                                                                                                              \
-        static bool attr_done = false;                                                                                \
-        if (!attr_done) {                                                                                             \
-            (void)hipFuncSetAttribute((const void*)conv_tile_kernel<MODE, N_, R_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                96 * 1024);                                                                           \
-            attr_done = true;                                                                                         \
-        }                                                                                                             \
+        if (int rc = otvae_lds_grant<&conv_tile_kernel<MODE, N_, R_>>(who, smem, 96 * 1024)) return rc;               \
         conv_tile_kernel<MODE, N_, R_><<<grid, 256, smem, st>>>(pl, S, scale, shift, relu, Wg, bias, res, y, xin, mean, \
                                                                 invstd, gv, partial, fold);                           \
     } while (0)
@@ -318,12 +314,8 @@ static int tile_pair_launch(const TileJobArgs& a, const TileJobArgs& b, size_t s
     const TilePairArgs t = {{a, b}, nb0};
 #define X(N0_, R0_, N1_, R1_)                                                                                         \
     if (a.pl.nt == N0_ && a.pl.rbw == R0_ && b.pl.nt == N1_ && b.pl.rbw == R1_) {                                     \
-        static bool attr_done = false;                                                                                \
-        if (!attr_done) {                                                                                             \
-            (void)hipFuncSetAttribute((const void*)conv_tile_kernel_pair<MODE, N0_, R0_, N1_, R1_>,                   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);                         \
-            attr_done = true;                                                                                         \
-        }                                                                                                             \
+        if (int rc = otvae_lds_grant<&conv_tile_kernel_pair<MODE, N0_, R0_, N1_, R1_>>("otvae_conv_multi(pair)", smem, 96 * 1024)) \
+            return rc;                                                                                                \
         conv_tile_kernel_pair<MODE, N0_, R0_, N1_, R1_><<<nb0 + nb1, 256, smem, st>>>(t);                             \
         return 0;                                                                                                     \
     }

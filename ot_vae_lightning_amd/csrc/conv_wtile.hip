@@ -333,12 +333,7 @@ int conv_wtile(const WTilePlan& plan, int nblocks, size_t smem, hipStream_t st, 
     if (((uintptr_t)gy & 15) != 0) pl.gvec = 0;  // unaligned output gradient: element-wise staging
 #define WT(K_, N_)                                                                                                        \
     do {                                                                                                                  \
-        static bool attr_done = false;                                                                                    \
-        if (!attr_done) {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)conv_wtile_kernel<K_, N_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      128 * 1024);                                                                        \
-            attr_done = true;                                                                                             \
-        }                                                                                                                 \
+        if (int rc = otvae_lds_grant<&conv_wtile_kernel<K_, N_>>("otvae_conv_bwd_weight(tile)", smem, 128 * 1024)) return rc; \
         conv_wtile_kernel<K_, N_><<<dim3(nblocks, pl.ny), 256, smem, st>>>(pl, x, scale, shift, relu, gy, partial);                    \
     } while (0)
     const int kt = pl.nkt;

@@ -539,19 +539,12 @@ __global__ __launch_bounds__(256) void hj_product_kernel(int D, void* __restrict
     if (i < D && j < D) ob[(size_t)i * D + j] = acc;
 }
 
-static bool g_hj_lds_set = false;
-
 int eigh_onesided(const double* A, int nb, int D, int fn, double* out, double* eigvals, void* ws, hipStream_t st, const double* Vinit,
                   double* g0, const int* warm) {
     const size_t lds = (size_t)((D + 1) & ~1) * (D + 1) * sizeof(double);  // n positions x (D + 1) rows
-    if (lds > 65536 && !g_hj_lds_set) {
-        // the kernel also holds 4 bytes of static LDS: ask for what D = 128 needs, not for the whole 160 KiB
-        if (hipFuncSetAttribute((const void*)hj_sweep_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 129 * 8) != hipSuccess) {
-            otvae_set_error("otvae_eigh_fn: cannot raise dynamic LDS limit");
-            return OTVAE_ELAUNCH;
-        }
-        g_hj_lds_set = true;
-    }
+    // (only D > 90, hence only hj_sweep_kernel<8>, crosses 64 KiB.)  The kernel also holds 4 bytes of static LDS: ask for what
+    // D = 128 needs, not for the whole 160 KiB
+    if (int rc = otvae_lds_grant<&hj_sweep_kernel<8>>("otvae_eigh_fn", lds, 128 * 129 * 8)) return rc;
     const double* G0 = nullptr;
     if (Vinit) {  // G0[b][j][:] = A_b v_j = row j of Vinit_b A_b (A symmetric)
         gemm_f64_launch(0, 0, nb, D, D, D, 1.0, Vinit, (size_t)D * D, A, (size_t)D * D, 0.0, g0, st);
@@ -1016,17 +1009,10 @@ __global__ __launch_bounds__(256) void hjb_finish_kernel(int D, int fn, void* __
 }
 
 
-static bool g_hjg_lds_set = false;
-
 int eigh_block_onesided(const double* A, int nb, int D, int fn, double* out, double* eigvals, void* ws, hipStream_t st) {
-    if (!g_hjg_lds_set) {
-        if (hipFuncSetAttribute((const void*)hjg_round_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(2 * HJB_B * (HJB_MAX_D + 1) * 8)) != hipSuccess) {
-            otvae_set_error("otvae_eigh_fn: cannot raise dynamic LDS limit");
-            return OTVAE_ELAUNCH;
-        }
-        g_hjg_lds_set = true;
-    }
+    // 16 columns of D + 1 doubles (D rounded up to 16): 18 KiB at D = 129, above 64 KiB from D = 497 on, 128 KiB at D = 1024
+    const size_t lds_g = (size_t)2 * HJB_B * (((D + 15) & ~15) + 1) * sizeof(double);
+    if (int rc = otvae_lds_grant<&hjg_round_kernel>("otvae_eigh_fn", lds_g, 2 * HJB_B * (HJB_MAX_D + 1) * 8)) return rc;
     const int Dp = hjb_dp(D), nblk = Dp / HJB_B;
     {  // L into the T area (free until the end), the pivot flag into the control block: the whole batch in the same launches
         const HjbWs w0 = hjb_ws(ws, 0, D);
@@ -1040,7 +1026,6 @@ int eigh_block_onesided(const double* A, int nb, int D, int fn, double* out, dou
     // still resident at once (two matrices of D = 1024 side by side are 128 rotation + 128 update blocks already)
     const int vslabs = (nblk / 2 * (1 + HJB_VSLABS) * nb <= 256) ? HJB_VSLABS : 1;
     const dim3 grid(nblk / 2 * (1 + vslabs), nb);  // rotation blocks, then the eigenvector-update blocks of the launch before
-    const size_t lds_g = (size_t)2 * HJB_B * (((D + 15) & ~15) + 1) * sizeof(double);
     auto round_launch = [&](int launch, int rotate) {
         hjg_round_kernel<<<grid, 512, lds_g, st>>>(D, launch, nrounds, rotate, vslabs, ws);
     };
@@ -1060,10 +1045,9 @@ int eigh_block_onesided(const double* A, int nb, int D, int fn, double* out, dou
         int* flags = nullptr;  // [HJB_MAX_SWEEPS], mapped host memory
         hipEvent_t ev[2];
     };
-    static FollowState follow_tab[16];
-    int follow_dev = -1;
-    bool follow = (cap == hipStreamCaptureStatusNone);
-    if (follow && (hipGetDevice(&follow_dev) != hipSuccess || follow_dev < 0 || follow_dev >= 16)) follow = false;
+    static FollowState follow_tab[OTVAE_MAX_DEVICES];
+    const int follow_dev = otvae_current_device();
+    bool follow = cap == hipStreamCaptureStatusNone && follow_dev >= 0 && follow_dev < OTVAE_MAX_DEVICES;  // (else: the blind budget)
     FollowState& fs = follow_tab[follow ? follow_dev : 0];
     std::unique_lock<std::mutex> follow_lock(fs.mu, std::defer_lock);
     if (follow) {

@@ -474,7 +474,6 @@ static size_t eigh_lds_bytes(int D) {
     const int De = (D + 1) & ~1, half = De / 2;
     return ((size_t)D * (D + 1) + 2 * half + 16) * sizeof(double) + (2 * half + 2) * sizeof(int);
 }
-static size_t g_eigh_lds_set = 0;
 
 extern "C" int otvae_eigh_fn(const double* A, int nb, int D, int fn, double* out, double* eigvals, void* ws, void* stream) {
     OTVAE_REQUIRE(A && eigvals && ws && nb > 0 && D > 0, "otvae_eigh_fn: bad argument");
@@ -485,13 +484,7 @@ extern "C" int otvae_eigh_fn(const double* A, int nb, int D, int fn, double* out
     if (D > EIGH_MAX_D) return eigh_block(A, nb, D, fn, out, eigvals, (double*)ws, (hipStream_t)stream);
     if (!getenv("OTVAE_EIGH_TWOSIDED")) return eigh_onesided(A, nb, D, fn, out, eigvals, ws, (hipStream_t)stream, nullptr, nullptr, nullptr);
     const size_t lds = eigh_lds_bytes(D);
-    if (lds > 65536 && lds > g_eigh_lds_set) {
-        if (hipFuncSetAttribute((const void*)eigh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            otvae_set_error("otvae_eigh_fn: cannot raise dynamic LDS limit");
-            return OTVAE_ELAUNCH;
-        }
-        g_eigh_lds_set = 160 * 1024;
-    }
+    if (int rc = otvae_lds_grant<&eigh_kernel>("otvae_eigh_fn", lds, 160 * 1024)) return rc;
     eigh_kernel<<<nb, EIGH_THREADS, lds, (hipStream_t)stream>>>(A, D, fn, out, eigvals, (double*)ws, nullptr);
     OTVAE_CHECK_LAUNCH("otvae_eigh_fn");
     return OTVAE_OK;

@@ -410,16 +410,9 @@ template <int NT, bool IMQ>
 static int mmd_launch(const float* z, const float* y, int N, int M, int D, const MmdPlan& p, const MmdFn& f, float czz, float czy,
                       int biased, int vec, double* kpart, float* gpart, hipStream_t st) {
     const size_t lds = mmd_lds_bytes(p);
-    static size_t lds_set = 0;   // per instantiation
-    if (lds > 65536 && lds > lds_set) {   // the kernel also has 32 bytes of static LDS: ask for what the widest D needs, not all 160 KiB
-        const size_t most = ((size_t)2 * MMD_TILE * (MMD_MAX_D + 4) + MMD_TILE * MMD_WLD + 4 * MMD_TILE) * sizeof(float);
-        if (hipFuncSetAttribute((const void*)mmd_fwd_kernel<NT, IMQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most) !=
-            hipSuccess) {
-            otvae_set_error("otvae_mmd_fwd: cannot raise the dynamic LDS limit to %zu bytes", most);
-            return OTVAE_ELAUNCH;
-        }
-        lds_set = most;
-    }
+    // the kernel also has 32 bytes of static LDS: ask for what the widest D needs, not all 160 KiB
+    const size_t most = ((size_t)2 * MMD_TILE * (MMD_MAX_D + 4) + MMD_TILE * MMD_WLD + 4 * MMD_TILE) * sizeof(float);
+    if (int rc = otvae_lds_grant<&mmd_fwd_kernel<NT, IMQ>>("otvae_mmd_fwd", lds, most)) return rc;
     mmd_fwd_kernel<NT, IMQ><<<dim3(p.nz + p.ny), 256, lds, st>>>(z, y, N, M, D, p, f, czz, czy, biased, vec, kpart, gpart);
     OTVAE_CHECK_LAUNCH("otvae_mmd_fwd(tiles)");
     return OTVAE_OK;

@@ -64,8 +64,6 @@ __global__ __launch_bounds__(256) void mvn_solve_kernel(const double* __restrict
     }
 }
 
-static bool g_mvn_lds_set[2] = {false, false};
-
 template <bool BWD>
 static int mvn_launch(const double* x, const double* mean, const double* L, const double* g, int nb, int B, int D, int diag,
                       double* out, double* lp, hipStream_t st, const char* who) {
@@ -75,14 +73,8 @@ static int mvn_launch(const double* x, const double* mean, const double* L, cons
         return OTVAE_EUNSUPPORTED;
     }
     const size_t lds = ((size_t)(diag ? D : D * D) + D) * sizeof(double);
-    if (lds > 65536 && !g_mvn_lds_set[BWD]) {
-        if (hipFuncSetAttribute((const void*)mvn_solve_kernel<false, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((MVN_MAX_D * MVN_MAX_D + MVN_MAX_D) * sizeof(double))) != hipSuccess) {
-            otvae_set_error("%s: cannot raise the dynamic LDS limit", who);
-            return OTVAE_ELAUNCH;
-        }
-        g_mvn_lds_set[BWD] = true;
-    }
+    // only the full-covariance kernel: the diagonal form holds 2 D doubles, 2 KiB at MVN_MAX_D, and never crosses 64 KiB
+    if (int rc = otvae_lds_grant<&mvn_solve_kernel<false, BWD>>(who, lds, (MVN_MAX_D * MVN_MAX_D + MVN_MAX_D) * sizeof(double))) return rc;
     const dim3 grid(cdiv(B, 256), nb);
     if (diag)
         mvn_solve_kernel<true, BWD><<<grid, 256, lds, st>>>(x, mean, L, g, B, D, out, lp);

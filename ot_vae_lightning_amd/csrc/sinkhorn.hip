@@ -334,14 +334,8 @@ static bool sk_with_rpw(int rpw, F f) {
 // workgroups that wait for each other must not be launched otherwise (false: nothing was launched).
 template <typename K, typename... Args>
 static bool sk_launch_resident(K kernel, int G, size_t lds, hipStream_t st, Args... args) {
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) n_cu = v;
-        if (n_cu <= 0) n_cu = 1;
-    }
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 512, lds) != hipSuccess || per_cu * n_cu < G) return false;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 512, lds) != hipSuccess || per_cu * otvae_cu_count() < G) return false;
     kernel<<<G, 512, lds, st>>>(args...);
     return true;
 }
