@@ -783,74 +783,6 @@ static void fwd_grid(const Geom& g, int& NT, dim3& grid, int& CnPad) {
     CnPad = ny * 16 * NT;
 }
 
-extern "C" int otvae_conv_fwd_stats_ws(const otvae_conv_geom* gg, int* P, int* CnPad) {
-    int rc = check_geom(gg, "otvae_conv_fwd_stats_ws");
-    if (rc) return rc;
-    Geom g = to_geom(gg);
-    int NT, cp;
-    dim3 grid;
-    fwd_grid(g, NT, grid, cp);
-    if (conv_small_ok(g)) grid.x = imin(grid.x, 1024);
-    TilePlan pl;
-    dim3 tg;
-    size_t sm;
-    if (!conv_small_ok(g) && conv_tile_plan(g, 0, pl, tg, sm)) {
-        grid.x = tg.x * tg.z;
-        cp = pl.cpad;
-    }
-    if (P) *P = grid.x;
-    if (CnPad) *CnPad = cp;
-    return OTVAE_OK;
-}
-
-static inline bool g_cs_le_tab(const otvae_conv_geom* g) { return g->Cs <= BN_TAB; }
-
-// the forward launch with its two round-4 extras: the BatchNorm of the input folded in (fold.slots != NULL), and the output's statistics
-// into slots instead of partials (stat_slots != NULL)
-static int conv_fwd_ex(const otvae_conv_geom* gg, const float* x, const float* scale, const float* shift, int relu, const float* wT,
-                       const float* bias, const float* residual, float* y, double* stat_dst, const BnFold& fold, void* stream) {
-    int rc = check_geom(gg, "otvae_conv_fwd");
-    if (rc) return rc;
-    OTVAE_REQUIRE(x && wT && y, "otvae_conv_fwd: NULL tensor");
-    OTVAE_REQUIRE((scale == nullptr) == (shift == nullptr), "otvae_conv_fwd: scale and shift must be given together");
-    OTVAE_REQUIRE(fold.slots == nullptr || g_cs_le_tab(gg), "otvae_conv_fwd: a folded BatchNorm takes at most %d channels", BN_TAB);
-    Geom g = to_geom(gg);
-    int NT, CnPad;
-    dim3 grid;
-    fwd_grid(g, NT, grid, CnPad);
-    if (conv_small_ok(g)) {
-        conv_small_fwd(g, imin(grid.x, 1024), x, scale, shift, relu, wT, bias, residual, y, stat_dst, CnPad, fold,
-                       (hipStream_t)stream);
-        OTVAE_CHECK_LAUNCH("otvae_conv_fwd(small)");
-        return OTVAE_OK;
-    }
-    {
-        TilePlan pl;
-        dim3 tg;
-        size_t sm;
-        if (conv_tile_plan(g, 0, pl, tg, sm)) {
-            OTVAE_REQUIRE(aligned16(x) && aligned16(wT) && aligned16(y) && (!bias || aligned16(bias)) &&
-                              (!residual || aligned16(residual)) && (!scale || (aligned16(scale) && aligned16(shift))),
-                          "otvae_conv_fwd: tensors of a layer with channel counts %% 4 == 0 must be 16-byte aligned");
-            rc = conv_tile_fwd(pl, tg, sm, (hipStream_t)stream, x, scale, shift, relu, wT, bias, residual, y, stat_dst, fold);
-            if (rc == OTVAE_ELAUNCH) return rc;
-            OTVAE_REQUIRE(rc == 0, "otvae_conv_fwd: no image-tile kernel for nt=%d rbw=%d", pl.nt, pl.rbw);
-            OTVAE_CHECK_LAUNCH("otvae_conv_fwd(tile)");
-            return OTVAE_OK;
-        }
-    }
-    launch_gemm<0>(NT, grid, (hipStream_t)stream, g, x, scale, shift, relu, wT, bias, residual, y, nullptr, nullptr, nullptr,
-                   nullptr, stat_dst, CnPad, fold);
-    OTVAE_CHECK_LAUNCH("otvae_conv_fwd");
-    return OTVAE_OK;
-}
-
-extern "C" int otvae_conv_fwd(const otvae_conv_geom* gg, const float* x, const float* scale, const float* shift, int relu,
-                              const float* wT, const float* bias, const float* residual, float* y, double* stat_partial,
-                              void* stream) {
-    return conv_fwd_ex(gg, x, scale, shift, relu, wT, bias, residual, y, stat_partial, BnFold{}, stream);
-}
-
 // ------------------------------------------------------------------------------------------------ weight transpose
 __global__ void weight_transpose_kernel(const float* __restrict__ wT, float* __restrict__ wD, int T, int Cs, int Cn) {
     const size_t total = (size_t)T * Cs * Cn;
@@ -909,78 +841,6 @@ static void dgrad_grid(const Geom& g, int& NT, dim3& grid, int& CsPad) {
     // bounded number of blocks (each writes one BatchNorm partial): <= 1024 over x*z
     grid = dim3(imax(1, imin(cdiv(rows, TM), 1024 / nz)), ny, nz);
     CsPad = ny * 16 * NT;
-}
-
-extern "C" int otvae_conv_bwd_data_ws(const otvae_conv_geom* gg, int* P, int* CsPad) {
-    int rc = check_geom(gg, "otvae_conv_bwd_data_ws");
-    if (rc) return rc;
-    Geom g = to_geom(gg);
-    int NT;
-    dim3 grid;
-    int cp;
-    dgrad_grid(g, NT, grid, cp);
-    TilePlan pl;
-    dim3 tg;
-    size_t sm;
-    if (!conv_small_ok(g) && conv_tile_plan(g, 1, pl, tg, sm)) {
-        grid = tg;
-        cp = pl.cpad;
-    }
-    if (P) *P = grid.x * grid.z;
-    if (CsPad) *CsPad = cp;
-    return OTVAE_OK;
-}
-
-// bn_partial: the [2][CsPad][P] partials, or tagged statistic slots (bn_tag_slots)
-static int conv_bwd_data_ex(const otvae_conv_geom* gg, const float* gy, const float* wD, const float* x, const float* scale,
-                            const float* shift, int relu, const float* mean, const float* invstd, float* gv, double* bn_partial,
-                            void* stream);
-
-extern "C" int otvae_conv_bwd_data(const otvae_conv_geom* gg, const float* gy, const float* wD, const float* x,
-                                   const float* scale, const float* shift, int relu, const float* mean, const float* invstd,
-                                   float* gv, double* bn_partial, void* stream) {
-    return conv_bwd_data_ex(gg, gy, wD, x, scale, shift, relu, mean, invstd, gv, bn_partial, stream);
-}
-
-static int conv_bwd_data_ex(const otvae_conv_geom* gg, const float* gy, const float* wD, const float* x, const float* scale,
-                            const float* shift, int relu, const float* mean, const float* invstd, float* gv, double* bn_partial,
-                            void* stream) {
-    int rc = check_geom(gg, "otvae_conv_bwd_data");
-    if (rc) return rc;
-    OTVAE_REQUIRE(gy && wD && gv, "otvae_conv_bwd_data: NULL tensor");
-    OTVAE_REQUIRE((scale == nullptr) == (shift == nullptr), "otvae_conv_bwd_data: scale/shift must come together");
-    OTVAE_REQUIRE((mean == nullptr) == (invstd == nullptr), "otvae_conv_bwd_data: mean/invstd must come together");
-    OTVAE_REQUIRE(!(relu || mean) || x, "otvae_conv_bwd_data: x needed for the ReLU mask / BatchNorm sums");
-    OTVAE_REQUIRE(!mean || bn_partial, "otvae_conv_bwd_data: bn_partial workspace missing");
-    Geom g = to_geom(gg);
-    int NT, CsPad;
-    dim3 grid;
-    dgrad_grid(g, NT, grid, CsPad);
-    if (conv_small_ok(g)) {  // same number of BatchNorm partials (grid.x * grid.z) as the workspace query promised
-        conv_small_dgrad(g, grid.x * grid.z, gy, wD, x, scale, shift, relu, mean, invstd, gv, bn_partial, CsPad,
-                         (hipStream_t)stream);
-        OTVAE_CHECK_LAUNCH("otvae_conv_bwd_data(small)");
-        return OTVAE_OK;
-    }
-    {
-        TilePlan pl;
-        dim3 tg;
-        size_t sm;
-        if (conv_tile_plan(g, 1, pl, tg, sm)) {
-            OTVAE_REQUIRE(aligned16(gy) && aligned16(wD) && aligned16(gv) && (!x || aligned16(x)) &&
-                              (!scale || (aligned16(scale) && aligned16(shift))) && (!mean || (aligned16(mean) && aligned16(invstd))),
-                          "otvae_conv_bwd_data: tensors of a layer with channel counts %% 4 == 0 must be 16-byte aligned");
-            rc = conv_tile_dgrad(pl, tg, sm, (hipStream_t)stream, gy, wD, x, scale, shift, relu, mean, invstd, gv, bn_partial);
-            if (rc == OTVAE_ELAUNCH) return rc;
-            OTVAE_REQUIRE(rc == 0, "otvae_conv_bwd_data: no image-tile kernel for nt=%d rbw=%d", pl.nt, pl.rbw);
-            OTVAE_CHECK_LAUNCH("otvae_conv_bwd_data(tile)");
-            return OTVAE_OK;
-        }
-    }
-    launch_gemm<1>(NT, grid, (hipStream_t)stream, g, gy, scale, shift, relu, wD, nullptr, nullptr, nullptr, x, mean, invstd, gv,
-                   bn_partial, CsPad);
-    OTVAE_CHECK_LAUNCH("otvae_conv_bwd_data");
-    return OTVAE_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ weight gradient
@@ -1352,90 +1212,87 @@ static void wgrad_plan(const Geom& g, int has_bias, int& NT, int& P, unsigned& c
     P = cdiv(M, chunk);
 }
 
-extern "C" int otvae_conv_bwd_weight_ws(const otvae_conv_geom* gg, int has_bias, int* P) {
-    int rc = check_geom(gg, "otvae_conv_bwd_weight_ws");
-    if (rc) return rc;
-    Geom g = to_geom(gg);
-    int NT, p, nkb, nnb, Kp;
-    unsigned chunk;
-    wgrad_plan(g, has_bias, NT, p, chunk, nkb, nnb, Kp);
-    {
-        WTilePlan wp;
-        int nbk;
-        size_t sm;
-        if (conv_wtile_plan(g, has_bias, wp, nbk, sm)) p = conv_wtile_nparts(nbk);
+// ------------------------------------------------------------------------------------------------ the plan of one job
+// Which kernel family serves a job, and with what grid, is decided ONCE, here, from the geometry alone (and the selection switches,
+// read per call inside the functions asked).  The workspace queries report the plan's `parts`; launch_planned launches with the same
+// number: a block writes one partial row, so the two can no longer disagree.  Pointer alignment is not part of the plan: it is a
+// predicate over a job's pointers (tile_aligned, gemm_vec_aligned), evaluated where the job is launched or packed.
+enum { ROUTE_DIRECT = 0, ROUTE_TILE = 1, ROUTE_GEMM = 2 };
+struct ConvPlan {
+    Geom g;
+    int kind, has_bias;  // OTVAE_JOB_*; has_bias: weight gradient only
+    int route;
+    bool ch4;            // both channel counts are multiples of 4: what the vector paths of the implicit GEMM need besides alignment
+    int NT, cpad;        // implicit GEMM: column tiles per wave; padded channel count of the statistics rows (ROUTE_TILE: the tile plan's)
+    dim3 grid;           // implicit GEMM (weight gradient: nkb x nnb x split-K partials)
+    int parts;           // statistics rows (forward), BatchNorm-backward rows (data gradient), split-K partials (weight gradient)
+    unsigned chunk;      // weight gradient: pixels per partial
+    int Kp, nkb, nnb;    // weight gradient: k-rows (+ bias row), 64-row k blocks, column blocks
+    TilePlan tile;       // ROUTE_TILE, forward / data gradient
+    dim3 tgrid;
+    WTilePlan wtile;     // ROUTE_TILE, weight gradient
+    int wblocks;
+    size_t lds;          // ROUTE_TILE: dynamic LDS bytes
+};
+
+static int conv_plan(const otvae_conv_geom* gg, int kind, int has_bias, const char* who, ConvPlan& p) {
+    OTVAE_REQUIRE(kind >= OTVAE_JOB_FWD && kind <= OTVAE_JOB_BWD_WEIGHT, "%s: bad kind %d", who, kind);
+    if (int rc = check_geom(gg, who)) return rc;
+    const Geom g = to_geom(gg);
+    p.g = g;
+    p.kind = kind;
+    p.has_bias = has_bias;
+    p.ch4 = (g.Cs % 4 == 0) && (g.Cn % 4 == 0);
+    if (kind == OTVAE_JOB_BWD_WEIGHT) {
+        int P;
+        wgrad_plan(g, has_bias, p.NT, P, p.chunk, p.nkb, p.nnb, p.Kp);
+        p.grid = dim3(p.nkb, p.nnb, P);
+        p.cpad = 0;
+        if (conv_wtile_plan(g, has_bias, p.wtile, p.wblocks, p.lds)) {
+            p.route = ROUTE_TILE;
+            p.parts = conv_wtile_nparts(p.wblocks);
+        } else {
+            p.route = conv_small_wgrad_ok(g) ? ROUTE_DIRECT : ROUTE_GEMM;
+            p.parts = P;
+        }
+        return OTVAE_OK;
     }
-    if (P) *P = p;
+    if (kind == OTVAE_JOB_FWD) fwd_grid(g, p.NT, p.grid, p.cpad);
+    else dgrad_grid(g, p.NT, p.grid, p.cpad);
+    p.parts = p.grid.x * p.grid.z;
+    if (conv_small_ok(g)) {
+        p.route = ROUTE_DIRECT;
+        if (kind == OTVAE_JOB_FWD) p.parts = imin(p.parts, 1024);
+    } else if (conv_tile_plan(g, kind, p.tile, p.tgrid, p.lds)) {  // mode 0 / 1 == OTVAE_JOB_FWD / OTVAE_JOB_BWD_DATA
+        p.route = ROUTE_TILE;
+        p.parts = p.tgrid.x * p.tgrid.z;
+        p.cpad = p.tile.cpad;
+    } else {
+        p.route = ROUTE_GEMM;
+    }
     return OTVAE_OK;
 }
 
-extern "C" int otvae_conv_bwd_weight(const otvae_conv_geom* gg, const float* x, const float* scale, const float* shift,
-                                     int relu, const float* gy, int has_bias, float* partial, float* gw, float* gb,
-                                     int defer_reduce, void* stream) {
-    int rc = check_geom(gg, "otvae_conv_bwd_weight");
-    if (rc) return rc;
-    OTVAE_REQUIRE(x && gy && partial && gw, "otvae_conv_bwd_weight: NULL tensor");
-    OTVAE_REQUIRE(!has_bias || gb, "otvae_conv_bwd_weight: gb missing");
-    OTVAE_REQUIRE((scale == nullptr) == (shift == nullptr), "otvae_conv_bwd_weight: scale/shift must come together");
-    Geom g = to_geom(gg);
-    int NT, P, nkb, nnb, Kp;
-    unsigned chunk;
-    wgrad_plan(g, has_bias, NT, P, chunk, nkb, nnb, Kp);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t total = (size_t)Kp * g.Cn;
-    {
-        WTilePlan wp;
-        int nbk;
-        size_t sm;
-        if (conv_wtile_plan(g, has_bias, wp, nbk, sm)) {
-            OTVAE_REQUIRE(!wp.vec4 || (aligned16(x) && (!scale || (aligned16(scale) && aligned16(shift)))),
-                          "otvae_conv_bwd_weight: x / scale / shift of a layer with Cs %% 4 == 0 must be 16-byte aligned");
-            rc = conv_wtile(wp, nbk, sm, st, x, scale, shift, relu, gy, partial);
-            if (rc) return rc;
-            OTVAE_CHECK_LAUNCH("otvae_conv_bwd_weight(tile)");
-            if (defer_reduce) return OTVAE_OK;
-            P = conv_wtile_nparts(nbk);
-            wgrad_reduce_kernel<<<imin(cdiv(total, P >= 32 ? 4 : 64), 2048), 256, 0, st>>>(partial, P, Kp - (has_bias ? 1 : 0),
-                                                                                         Kp, g.Cn, gw, gb);
-            OTVAE_CHECK_LAUNCH("otvae_conv_bwd_weight(reduce)");
-            return OTVAE_OK;
-        }
-    }
-    if (conv_small_wgrad_ok(g)) {
-        conv_small_wgrad(g, x, scale, shift, relu, gy, has_bias, partial, st);
-        OTVAE_CHECK_LAUNCH("otvae_conv_bwd_weight(small)");
-        if (defer_reduce) return OTVAE_OK;
-        wgrad_reduce_kernel<<<imin(cdiv(total, P >= 32 ? 4 : 64), 2048), 256, 0, st>>>(partial, P, Kp - (has_bias ? 1 : 0), Kp,
-                                                                                     g.Cn, gw, gb);
-        OTVAE_CHECK_LAUNCH("otvae_conv_bwd_weight(reduce)");
-        return OTVAE_OK;
-    }
-    dim3 grid(nkb, nnb, P);
-    const bool vec = (g.Cs % 4 == 0) && (g.Cn % 4 == 0) && aligned16(x) && aligned16(gy) &&
-                     (scale == nullptr || (aligned16(scale) && aligned16(shift)));
-#define OTVAE_WG(N_, V_) \
-    conv_wgrad_kernel<N_, V_><<<grid, 256, 0, st>>>(g, x, scale, shift, relu, gy, partial, Kp, has_bias, \
-                                                    defer_reduce == OTVAE_DEFER_SPARSE, chunk)
-    if (vec) {
-        switch (NT) {
-            case 1: OTVAE_WG(1, true); break;
-            case 2: OTVAE_WG(2, true); break;
-            case 3: OTVAE_WG(3, true); break;
-            default: OTVAE_WG(4, true); break;
-        }
-    } else {
-        switch (NT) {
-            case 1: OTVAE_WG(1, false); break;
-            case 2: OTVAE_WG(2, false); break;
-            case 3: OTVAE_WG(3, false); break;
-            default: OTVAE_WG(4, false); break;
-        }
-    }
-#undef OTVAE_WG
-    OTVAE_CHECK_LAUNCH("otvae_conv_bwd_weight");
-    if (defer_reduce) return OTVAE_OK;
-    wgrad_reduce_kernel<<<imin(cdiv(total, P >= 32 ? 4 : 64), 2048), 256, 0, st>>>(partial, P, Kp - (has_bias ? 1 : 0), Kp, g.Cn, gw, gb);
-    OTVAE_CHECK_LAUNCH("otvae_conv_bwd_weight(reduce)");
+extern "C" int otvae_conv_fwd_stats_ws(const otvae_conv_geom* gg, int* P, int* CnPad) {
+    ConvPlan p;
+    if (int rc = conv_plan(gg, OTVAE_JOB_FWD, 0, "otvae_conv_fwd_stats_ws", p)) return rc;
+    if (P) *P = p.parts;
+    if (CnPad) *CnPad = p.cpad;
+    return OTVAE_OK;
+}
+
+extern "C" int otvae_conv_bwd_data_ws(const otvae_conv_geom* gg, int* P, int* CsPad) {
+    ConvPlan p;
+    if (int rc = conv_plan(gg, OTVAE_JOB_BWD_DATA, 0, "otvae_conv_bwd_data_ws", p)) return rc;
+    if (P) *P = p.parts;
+    if (CsPad) *CsPad = p.cpad;
+    return OTVAE_OK;
+}
+
+extern "C" int otvae_conv_bwd_weight_ws(const otvae_conv_geom* gg, int has_bias, int* P) {
+    ConvPlan p;
+    if (int rc = conv_plan(gg, OTVAE_JOB_BWD_WEIGHT, has_bias, "otvae_conv_bwd_weight_ws", p)) return rc;
+    if (P) *P = p.parts;
     return OTVAE_OK;
 }
 
@@ -1555,22 +1412,17 @@ extern "C" int otvae_conv_dead_taps(const otvae_conv_geom* gg, uint32_t* mask) {
 // weight and scale / shift pointers (whole tensors from torch's allocator are).  A call with a misaligned pointer falls to the
 // scalar path, where per_tile would equal launch_rule.
 extern "C" int otvae_conv_gemm_chunks(const otvae_conv_geom* gg, int mode, int64_t* launch_rule, int64_t* per_tile) {
-    int rc = check_geom(gg, "otvae_conv_gemm_chunks");
-    if (rc) return rc;
-    OTVAE_REQUIRE(mode == 0 || mode == 1, "otvae_conv_gemm_chunks: mode must be 0 (forward) or 1 (data gradient)");
+    OTVAE_REQUIRE(mode == 0 || mode == 1,"otvae_conv_gemm_chunks: mode must be 0 (forward) or 1 (data gradient)");
     OTVAE_REQUIRE(launch_rule && per_tile, "otvae_conv_gemm_chunks: NULL argument");
-    const Geom g = to_geom(gg);
-    {
-        TilePlan pl;
-        dim3 tg;
-        size_t sm;
-        if (conv_small_ok(g) || conv_tile_plan(g, mode, pl, tg, sm)) {
-            otvae_set_error("otvae_conv_gemm_chunks: not served by the implicit GEMM (%s kernels take this layer)",
-                            conv_small_ok(g) ? "the direct" : "the image-tile");
-            return OTVAE_EUNSUPPORTED;
-        }
+    ConvPlan plan;
+    if (int rc = conv_plan(gg, mode, 0, "otvae_conv_gemm_chunks", plan)) return rc;  // mode 0 / 1 == OTVAE_JOB_FWD / OTVAE_JOB_BWD_DATA
+    if (plan.route != ROUTE_GEMM) {
+        otvae_set_error("otvae_conv_gemm_chunks: not served by the implicit GEMM (%s kernels take this layer)",
+                        plan.route == ROUTE_DIRECT ? "the direct" : "the image-tile");
+        return OTVAE_EUNSUPPORTED;
     }
-    const bool vec = (g.Cs % 4 == 0) && (g.Cn % 4 == 0);
+    const Geom& g = plan.g;
+    const bool vec = plan.ch4;
     const int Hu = g.Hs * g.up, Wu = g.Ws * g.up;
     const int lim_y = mode == 0 ? Hu : g.Ho * g.stride, lim_x = mode == 0 ? Wu : g.Wo * g.stride;
     const int last_y = mode == 0 ? (g.Ho - 1) * g.stride : Hu - 1, last_x = mode == 0 ? (g.Wo - 1) * g.stride : Wu - 1;
@@ -1750,6 +1602,225 @@ static size_t job_smem_bytes(int kind, int NT) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ one job: check, launch
+// Every entry point that launches a convolution (otvae_conv_fwd / _bwd_data / _bwd_weight and otvae_conv_multi) fills an
+// otvae_conv_job and takes it through the same steps: conv_plan (kind and geometry), check_job (the arguments), launch_planned.
+static int job_refused(const char* who, int index, const char* what) {
+    if (index >= 0) otvae_set_error("%s: job %d: %s", who, index, what);
+    else otvae_set_error("%s: %s", who, what);
+    return OTVAE_EINVAL;
+}
+#define OTVAE_STR_(x) #x
+#define OTVAE_STR(x) OTVAE_STR_(x)
+#define JOB_REQUIRE(cond, what)                            \
+    do {                                                   \
+        if (!(cond)) return job_refused(who, index, what); \
+    } while (0)
+
+// The argument checks of a job whose kind and geometry conv_plan has accepted; index >= 0: job `index` of an otvae_conv_multi call.
+static int check_job(const otvae_conv_job& jb, const char* who, int index) {
+    const char* const slots_rule = "statistic slots must be 16-byte aligned with a power of two <= 64 slots in use";
+    JOB_REQUIRE((jb.scale == nullptr) == (jb.shift == nullptr), "scale and shift must be given together");
+    JOB_REQUIRE(jb.kind == OTVAE_JOB_FWD || (jb.fold.slots == nullptr && jb.stat_slots == nullptr),
+                "fold / stat_slots belong to forward jobs");
+    switch (jb.kind) {
+        case OTVAE_JOB_FWD:
+            JOB_REQUIRE(jb.x && jb.w && jb.y, "NULL tensor");
+            JOB_REQUIRE(!(jb.stat_partial && jb.stat_slots), "statistics go to partials OR to slots");
+            JOB_REQUIRE(!jb.stat_slots || (aligned16(jb.stat_slots) && bn_slots_ok(jb.stat_nslots)), slots_rule);
+            JOB_REQUIRE(jb.fold.slots == nullptr || jb.geom.Cs <= BN_TAB,
+                        "a folded BatchNorm takes at most " OTVAE_STR(BN_TAB) " channels");
+            return OTVAE_OK;
+        case OTVAE_JOB_BWD_DATA:
+            JOB_REQUIRE(jb.gy && jb.w && jb.gv, "NULL tensor");
+            JOB_REQUIRE((jb.mean == nullptr) == (jb.invstd == nullptr), "mean and invstd must be given together");
+            JOB_REQUIRE(!(jb.relu || jb.mean) || jb.x, "x needed for the ReLU mask / BatchNorm sums");
+            JOB_REQUIRE(!jb.mean || jb.bn_partial || jb.bn_slots, "bn_partial workspace / bn_slots missing");
+            JOB_REQUIRE(!(jb.bn_partial && jb.bn_slots), "BatchNorm-backward sums go to partials OR to slots");
+            JOB_REQUIRE(!jb.bn_slots || (aligned16(jb.bn_slots) && bn_slots_ok(jb.bn_nslots)), slots_rule);
+            return OTVAE_OK;
+        default:
+            JOB_REQUIRE(jb.x && jb.gy && jb.wpartial && jb.gw, "NULL tensor");
+            JOB_REQUIRE(!jb.has_bias || jb.gb, "gb missing");
+            return OTVAE_OK;
+    }
+}
+#undef JOB_REQUIRE
+
+// The operands of a checked job in the form the kernels take them (the packed launch passes this struct by value), with the grid and
+// the tile shape of the implicit GEMM from the plan.  Fails only on an incomplete BatchNorm fold descriptor.
+static int dev_job(const ConvPlan& p, const otvae_conv_job& jb, const char* who, DevJob& d) {
+    d = {};
+    d.g = p.g;
+    d.kind = p.kind;
+    d.relu = jb.relu;
+    d.scale = jb.scale;
+    d.shift = jb.shift;
+    d.NT = p.NT;
+    d.cpad = p.cpad;
+    d.gx = p.grid.x, d.gy = p.grid.y, d.gz = p.grid.z;
+    switch (p.kind) {
+        case OTVAE_JOB_FWD:
+            if (int rc = bn_fold_from_abi(who, jb.fold, p.g.Cs, &d.fold)) return rc;
+            d.a0 = jb.x;
+            d.b0 = jb.w;
+            d.bias = jb.bias;
+            d.res = jb.residual;
+            d.out = jb.y;
+            d.partial = jb.stat_slots ? bn_tag_slots(jb.stat_slots, jb.stat_nslots) : jb.stat_partial;
+            break;
+        case OTVAE_JOB_BWD_DATA:
+            d.a0 = jb.gy;
+            d.b0 = jb.w;
+            d.xin = jb.x;
+            d.mean = jb.mean;
+            d.invstd = jb.invstd;
+            d.out = jb.gv;
+            d.partial = jb.bn_slots ? bn_tag_slots(jb.bn_slots, jb.bn_nslots) : jb.bn_partial;
+            break;
+        default:
+            d.a0 = jb.x;
+            d.b0 = jb.gy;
+            d.out = jb.wpartial;
+            d.Kp = p.Kp;
+            d.chunk = p.chunk;
+            d.has_bias = jb.has_bias;
+            d.skip_dead = jb.defer_reduce == OTVAE_DEFER_SPARSE;
+            break;
+    }
+    return OTVAE_OK;
+}
+
+// ---- pointer alignment: predicates over a job's operands (a NULL pointer counts as aligned)
+// what the image-tile kernels require of every tensor they are handed (weight gradient: of x / scale / shift when Cs % 4 == 0)
+static bool tile_aligned(const ConvPlan& p, const DevJob& d) {
+    if (p.kind == OTVAE_JOB_BWD_WEIGHT) return !p.wtile.vec4 || (aligned16(d.a0) && aligned16(d.scale) && aligned16(d.shift));
+    const void* const ptrs[] = {d.a0, d.b0, d.out, d.bias, d.res, d.xin, d.scale, d.shift, d.mean, d.invstd};
+    for (const void* q : ptrs)
+        if (!aligned16(q)) return false;
+    return true;
+}
+// what the vector path of the implicit GEMM needs inside a packed launch (a one-job launch tests the same, in launch_gemm and in
+// launch_planned, and falls to the scalar path): the two GEMM operands, and the affine where the staging reads it as float4
+static bool gemm_vec_aligned(const DevJob& d) {
+    return aligned16(d.a0) && aligned16(d.b0) && (d.kind == OTVAE_JOB_BWD_DATA || (aligned16(d.scale) && aligned16(d.shift)));
+}
+
+// the immediate split-K reduction of a weight-gradient job: partial[parts][Kp][Cn] -> gw (+ gb)
+static int wgrad_reduce_now(const ConvPlan& p, const float* partial, float* gw, float* gb, const char* who, hipStream_t st) {
+    const int P = p.parts, Kp = p.Kp;
+    const size_t total = (size_t)Kp * p.g.Cn;
+    wgrad_reduce_kernel<<<imin(cdiv(total, P >= 32 ? 4 : 64), 2048), 256, 0, st>>>(partial, P, Kp - (p.has_bias ? 1 : 0), Kp, p.g.Cn, gw, gb);
+    OTVAE_CHECK_LAUNCH(who);
+    return OTVAE_OK;
+}
+
+// One job, on the route and with the grid of its plan.  d = dev_job(p, jb); jb itself is read for the weight gradient's reduction only.
+// An image-tile launch refuses misaligned tensors, and hands a refused LDS grant (OTVAE_ELAUNCH, error text set) up as it is.
+static int launch_planned(const ConvPlan& p, const otvae_conv_job& jb, const DevJob& d, const char* who, hipStream_t st) {
+    const Geom& g = p.g;
+    if (p.route == ROUTE_TILE)
+        OTVAE_REQUIRE(tile_aligned(p, d), "%s: tensors of an image-tile layer with channel counts %% 4 == 0 must be 16-byte aligned", who);
+    if (p.kind != OTVAE_JOB_BWD_WEIGHT) {
+        const bool fwd = p.kind == OTVAE_JOB_FWD;
+        if (p.route == ROUTE_DIRECT) {
+            if (fwd) conv_small_fwd(g, p.parts, d.a0, d.scale, d.shift, d.relu, d.b0, d.bias, d.res, d.out, d.partial, p.cpad, d.fold, st);
+            else conv_small_dgrad(g, p.parts, d.a0, d.b0, d.xin, d.scale, d.shift, d.relu, d.mean, d.invstd, d.out, d.partial, p.cpad, st);
+        } else if (p.route == ROUTE_TILE) {
+            const int rc = fwd ? conv_tile_fwd(p.tile, p.tgrid, p.lds, st, d.a0, d.scale, d.shift, d.relu, d.b0, d.bias, d.res, d.out,
+                                               d.partial, d.fold)
+                               : conv_tile_dgrad(p.tile, p.tgrid, p.lds, st, d.a0, d.b0, d.xin, d.scale, d.shift, d.relu, d.mean, d.invstd,
+                                                 d.out, d.partial);
+            if (rc == OTVAE_ELAUNCH) return rc;
+            OTVAE_REQUIRE(rc == 0, "%s: no image-tile kernel for nt=%d rbw=%d", who, p.tile.nt, p.tile.rbw);
+        } else if (fwd) {
+            launch_gemm<0>(p.NT, p.grid, st, g, d.a0, d.scale, d.shift, d.relu, d.b0, d.bias, d.res, d.out, nullptr, nullptr, nullptr, nullptr,
+                           d.partial, p.cpad, d.fold);
+        } else {
+            launch_gemm<1>(p.NT, p.grid, st, g, d.a0, d.scale, d.shift, d.relu, d.b0, nullptr, nullptr, nullptr, d.xin, d.mean, d.invstd, d.out,
+                           d.partial, p.cpad);
+        }
+        OTVAE_CHECK_LAUNCH(who);
+        return OTVAE_OK;
+    }
+    const float *x = d.a0, *scale = d.scale, *shift = d.shift, *gy = d.b0;
+    float* partial = d.out;
+    const int relu = d.relu, has_bias = d.has_bias, defer_reduce = jb.defer_reduce, Kp = p.Kp;
+    const unsigned chunk = p.chunk;
+    if (p.route == ROUTE_TILE) {
+        if (int rc = conv_wtile(p.wtile, p.wblocks, p.lds, st, x, scale, shift, relu, gy, partial)) return rc;
+    } else if (p.route == ROUTE_DIRECT) {
+        conv_small_wgrad(g, x, scale, shift, relu, gy, has_bias, partial, st);
+    } else {
+        const dim3 grid = p.grid;
+        const bool vec = p.ch4 && aligned16(x) && aligned16(gy) && aligned16(scale) && aligned16(shift);
+#define OTVAE_WG(N_, V_) \
+    conv_wgrad_kernel<N_, V_><<<grid, 256, 0, st>>>(g, x, scale, shift, relu, gy, partial, Kp, has_bias, \
+                                                    defer_reduce == OTVAE_DEFER_SPARSE, chunk)
+        if (vec) {
+            switch (p.NT) {
+                case 1: OTVAE_WG(1, true); break;
+                case 2: OTVAE_WG(2, true); break;
+                case 3: OTVAE_WG(3, true); break;
+                default: OTVAE_WG(4, true); break;
+            }
+        } else {
+            switch (p.NT) {
+                case 1: OTVAE_WG(1, false); break;
+                case 2: OTVAE_WG(2, false); break;
+                case 3: OTVAE_WG(3, false); break;
+                default: OTVAE_WG(4, false); break;
+            }
+        }
+#undef OTVAE_WG
+    }
+    OTVAE_CHECK_LAUNCH(who);
+    return defer_reduce ? OTVAE_OK : wgrad_reduce_now(p, partial, jb.gw, jb.gb, who, st);
+}
+
+// the one-job entry points: plan, check, launch
+static int run_one_job(const otvae_conv_geom* gg, otvae_conv_job& jb, const char* who, void* stream) {
+    ConvPlan p;
+    if (int rc = conv_plan(gg, jb.kind, jb.has_bias, who, p)) return rc;  // (refuses a NULL geometry)
+    jb.geom = *gg;
+    if (int rc = check_job(jb, who, -1)) return rc;
+    DevJob d;
+    if (int rc = dev_job(p, jb, who, d)) return rc;
+    return launch_planned(p, jb, d, who, (hipStream_t)stream);
+}
+
+extern "C" int otvae_conv_fwd(const otvae_conv_geom* gg, const float* x, const float* scale, const float* shift, int relu,
+                              const float* wT, const float* bias, const float* residual, float* y, double* stat_partial,
+                              void* stream) {
+    otvae_conv_job jb = {};
+    jb.kind = OTVAE_JOB_FWD;
+    jb.x = x, jb.scale = scale, jb.shift = shift, jb.relu = relu, jb.w = wT, jb.bias = bias, jb.residual = residual, jb.y = y;
+    jb.stat_partial = stat_partial;
+    return run_one_job(gg, jb, "otvae_conv_fwd", stream);
+}
+
+// bn_partial: the [2][CsPad][P] partials, or tagged statistic slots (bn_tag_slots)
+extern "C" int otvae_conv_bwd_data(const otvae_conv_geom* gg, const float* gy, const float* wD, const float* x,
+                                   const float* scale, const float* shift, int relu, const float* mean, const float* invstd,
+                                   float* gv, double* bn_partial, void* stream) {
+    otvae_conv_job jb = {};
+    jb.kind = OTVAE_JOB_BWD_DATA;
+    jb.gy = gy, jb.w = wD, jb.x = x, jb.scale = scale, jb.shift = shift, jb.relu = relu, jb.mean = mean, jb.invstd = invstd, jb.gv = gv;
+    jb.bn_partial = bn_partial;
+    return run_one_job(gg, jb, "otvae_conv_bwd_data", stream);
+}
+
+extern "C" int otvae_conv_bwd_weight(const otvae_conv_geom* gg, const float* x, const float* scale, const float* shift,
+                                     int relu, const float* gy, int has_bias, float* partial, float* gw, float* gb,
+                                     int defer_reduce, void* stream) {
+    otvae_conv_job jb = {};
+    jb.kind = OTVAE_JOB_BWD_WEIGHT;
+    jb.x = x, jb.scale = scale, jb.shift = shift, jb.relu = relu, jb.gy = gy, jb.has_bias = has_bias, jb.wpartial = partial;
+    jb.gw = gw, jb.gb = gb, jb.defer_reduce = defer_reduce;
+    return run_one_job(gg, jb, "otvae_conv_bwd_weight", stream);
+}
+
+// ------------------------------------------------------------------------------------------------ otvae_conv_multi
 // kernel launches of the calling thread's last otvae_conv_multi (the immediate weight-gradient reductions included)
 static thread_local int g_multi_launches = 0;
 
@@ -1766,41 +1837,39 @@ static inline bool pair_launch_on() {
     return !(e && e[0] == '0' && e[1] == '\0');
 }
 
+// a forward / data-gradient job of the direct (PAIR_SMALL) or image-tile (PAIR_TILE) kernels, which may share a launch with its sibling
 enum { PAIR_NONE = 0, PAIR_SMALL = 1, PAIR_TILE = 2 };
 struct PairJob {
-    int idx, cls, kind;  // index in the call; PAIR_SMALL / PAIR_TILE; OTVAE_JOB_FWD / OTVAE_JOB_BWD_DATA
+    int idx, cls;  // index in the call (< 0: none); PAIR_SMALL / PAIR_TILE
+    ConvPlan plan;
     DevJob d;
-    TilePlan pl;         // PAIR_TILE
-    dim3 tg;
-    size_t smem;
 };
 
 static TileJobArgs tile_args(const PairJob& p) {
     const DevJob& d = p.d;
     TileJobArgs a = {};
-    a.pl = p.pl;
+    a.pl = p.plan.tile;
     a.S = d.a0, a.scale = d.scale, a.shift = d.shift, a.Wg = d.b0, a.bias = d.bias, a.res = d.res;
     a.xin = d.xin, a.mean = d.mean, a.invstd = d.invstd, a.partial = d.partial, a.fold = d.fold, a.relu = d.relu;
-    if (p.kind == OTVAE_JOB_FWD) a.y = d.out;
+    if (d.kind == OTVAE_JOB_FWD) a.y = d.out;
     else a.gv = d.out;
-    a.gx = p.tg.x, a.gy = p.tg.y, a.gz = p.tg.z;
+    a.gx = p.plan.tgrid.x, a.gy = p.plan.tgrid.y, a.gz = p.plan.tgrid.z;
     return a;
 }
 
-// both jobs (same class, same kind) in one launch, in the order given; -1, nothing launched, when there is no two-job kernel for them
+// both jobs (same class, same kind) in one launch, in the order given, each with the block count and the padded channel count of its
+// plan; -1, nothing launched, when there is no two-job kernel for them
 static int launch_pair_ordered(const PairJob& p, const PairJob& q, hipStream_t st) {
-    if (p.cls == PAIR_TILE)
-        return conv_tile_pair(p.kind == OTVAE_JOB_FWD ? 0 : 1, tile_args(p), tile_args(q), p.smem > q.smem ? p.smem : q.smem, st);
-    if (p.kind == OTVAE_JOB_FWD) {
-        // block counts, as conv_fwd_ex gives the one-job launch
-        const DevJob &a = p.d, &b = q.d;
-        const SmallFwdArgs fa = {a.g, a.a0, a.scale, a.shift, a.b0, a.bias, a.res, a.out, a.partial, a.fold, a.relu, a.cpad, imin(a.gx, 1024)};
-        const SmallFwdArgs fb = {b.g, b.a0, b.scale, b.shift, b.b0, b.bias, b.res, b.out, b.partial, b.fold, b.relu, b.cpad, imin(b.gx, 1024)};
+    const DevJob &a = p.d, &b = q.d;
+    const ConvPlan &pa = p.plan, &pb = q.plan;
+    if (p.cls == PAIR_TILE) return conv_tile_pair(pa.kind, tile_args(p), tile_args(q), pa.lds > pb.lds ? pa.lds : pb.lds, st);
+    if (pa.kind == OTVAE_JOB_FWD) {
+        const SmallFwdArgs fa = {a.g, a.a0, a.scale, a.shift, a.b0, a.bias, a.res, a.out, a.partial, a.fold, a.relu, pa.cpad, pa.parts};
+        const SmallFwdArgs fb = {b.g, b.a0, b.scale, b.shift, b.b0, b.bias, b.res, b.out, b.partial, b.fold, b.relu, pb.cpad, pb.parts};
         return conv_small_fwd_pair(fa, fb, st);
     }
-    const DevJob &a = p.d, &b = q.d;  // block counts, as conv_bwd_data_ex
-    const SmallDgradArgs da = {a.g, a.a0, a.b0, a.xin, a.scale, a.shift, a.mean, a.invstd, a.out, a.partial, a.relu, a.cpad, a.gx * a.gz};
-    const SmallDgradArgs db = {b.g, b.a0, b.b0, b.xin, b.scale, b.shift, b.mean, b.invstd, b.out, b.partial, b.relu, b.cpad, b.gx * b.gz};
+    const SmallDgradArgs da = {a.g, a.a0, a.b0, a.xin, a.scale, a.shift, a.mean, a.invstd, a.out, a.partial, a.relu, pa.cpad, pa.parts};
+    const SmallDgradArgs db = {b.g, b.a0, b.b0, b.xin, b.scale, b.shift, b.mean, b.invstd, b.out, b.partial, b.relu, pb.cpad, pb.parts};
     return conv_small_dgrad_pair(da, db, st);
 }
 
@@ -1811,22 +1880,10 @@ static int launch_pair(const PairJob& p, const PairJob& q, hipStream_t st) {
     return rc == -1 ? launch_pair_ordered(q, p, st) : rc;  // (OTVAE_ELAUNCH, a refused LDS grant, goes up as it is)
 }
 
-static int run_single_job(const otvae_conv_job& jb, void* stream) {
+// a job of the call in a launch of its own (plus the launch of its immediate reduction), from the plan made when it arrived
+static int run_single_job(const ConvPlan& p, const otvae_conv_job& jb, const DevJob& d, hipStream_t st) {
     g_multi_launches += (jb.kind == OTVAE_JOB_BWD_WEIGHT && !jb.defer_reduce) ? 2 : 1;
-    switch (jb.kind) {
-        case OTVAE_JOB_FWD: {
-            BnFold fold;
-            if (int rc = bn_fold_from_abi("otvae_conv_multi", jb.fold, jb.geom.Cs, &fold)) return rc;
-            return conv_fwd_ex(&jb.geom, jb.x, jb.scale, jb.shift, jb.relu, jb.w, jb.bias, jb.residual, jb.y,
-                               jb.stat_slots ? bn_tag_slots(jb.stat_slots, jb.stat_nslots) : jb.stat_partial, fold, stream);
-        }
-        case OTVAE_JOB_BWD_DATA:
-            return conv_bwd_data_ex(&jb.geom, jb.gy, jb.w, jb.x, jb.scale, jb.shift, jb.relu, jb.mean, jb.invstd, jb.gv,
-                                    jb.bn_slots ? bn_tag_slots(jb.bn_slots, jb.bn_nslots) : jb.bn_partial, stream);
-        default:
-            return otvae_conv_bwd_weight(&jb.geom, jb.x, jb.scale, jb.shift, jb.relu, jb.gy, jb.has_bias, jb.wpartial, jb.gw,
-                                         jb.gb, jb.defer_reduce, stream);
-    }
+    return launch_planned(p, jb, d, "otvae_conv_multi", st);
 }
 
 // what the calling thread's last otvae_conv_multi did with its jobs (bit i: job i ran inside a packed conv_jobs_kernel launch)
@@ -1841,6 +1898,7 @@ extern "C" int otvae_conv_multi_last(unsigned* packed_mask, int* uniform_tap) {
 }
 
 extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream) {
+    const char* const who = "otvae_conv_multi";
     OTVAE_REQUIRE(n > 0 && jobs, "otvae_conv_multi: no jobs");
     hipStream_t st = (hipStream_t)stream;
     g_multi_packed_mask = 0;
@@ -1849,156 +1907,77 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
     const bool pair_on = pair_launch_on();
     // The direct / image-tile job waiting for its sibling (idx < 0: none).  Like the jobs collected in `pack`, it is launched when a job
     // that cannot join it arrives, or at the end of the call: a call that returns an error for a later job has launched neither.
-    PairJob pend = {};
+    PairJob pend;
     pend.idx = -1;
     auto flush_pend = [&]() -> int {
         if (pend.idx < 0) return OTVAE_OK;
         const int i = pend.idx;
         pend.idx = -1;
-        return run_single_job(jobs[i], stream);
+        return run_single_job(pend.plan, jobs[i], pend.d, st);
     };
     DevJobs pack = {};
+    ConvPlan packed_plan[CJ_MAX];
+    int packed_idx[CJ_MAX];
     size_t smem = 0;
     int nblocks = 0;
-    int packed_idx[CJ_MAX];
     int pack_ut = -1;  // uniform-tap flavour of the packed forward / data-gradient jobs (-1: none yet)
     auto flush = [&]() -> int {
         if (pack.n == 0) return OTVAE_OK;
+        int rc = OTVAE_OK;
         if (pack.n == 1) {  // nothing to share a launch with: the dedicated kernel (static LDS, same body)
-            int rc = run_single_job(jobs[packed_idx[0]], stream);
-            pack = {};
-            smem = 0;
-            nblocks = 0;
-            pack_ut = -1;
-            return rc;
-        }
-        const bool live = gemm_live_taps();
-        if (pack_ut == 1) {
-            if (live) conv_jobs_kernel<true><<<nblocks, 256, smem, st>>>(pack);
-            else conv_jobs_rowmajor_kernel<true><<<nblocks, 256, smem, st>>>(pack);
+            rc = run_single_job(packed_plan[0], jobs[packed_idx[0]], pack.j[0], st);
         } else {
-            if (live) conv_jobs_kernel<false><<<nblocks, 256, smem, st>>>(pack);
-            else conv_jobs_rowmajor_kernel<false><<<nblocks, 256, smem, st>>>(pack);
-        }
-        OTVAE_CHECK_LAUNCH("otvae_conv_multi");
-        ++g_multi_launches;
-        for (int i = 0; i < pack.n; ++i) g_multi_packed_mask |= 1u << packed_idx[i];
-        g_multi_packed_ut = pack_ut == 1 ? 1 : 0;
-        for (int i = 0; i < pack.n; ++i) {  // immediate reductions of the packed weight-gradient jobs
-            const otvae_conv_job& jb = jobs[packed_idx[i]];
-            if (jb.kind != OTVAE_JOB_BWD_WEIGHT || jb.defer_reduce) continue;
-            const DevJob& d = pack.j[i];
-            const size_t total = (size_t)d.Kp * d.g.Cn;
-            wgrad_reduce_kernel<<<imin(cdiv(total, d.gz >= 32 ? 4 : 64), 2048), 256, 0, st>>>(
-                jb.wpartial, d.gz, d.Kp - (jb.has_bias ? 1 : 0), d.Kp, d.g.Cn, jb.gw, jb.gb);
-            OTVAE_CHECK_LAUNCH("otvae_conv_multi(reduce)");
+            const bool live = gemm_live_taps();
+            if (pack_ut == 1) {
+                if (live) conv_jobs_kernel<true><<<nblocks, 256, smem, st>>>(pack);
+                else conv_jobs_rowmajor_kernel<true><<<nblocks, 256, smem, st>>>(pack);
+            } else {
+                if (live) conv_jobs_kernel<false><<<nblocks, 256, smem, st>>>(pack);
+                else conv_jobs_rowmajor_kernel<false><<<nblocks, 256, smem, st>>>(pack);
+            }
+            OTVAE_CHECK_LAUNCH("otvae_conv_multi");
             ++g_multi_launches;
+            for (int i = 0; i < pack.n; ++i) g_multi_packed_mask |= 1u << packed_idx[i];
+            g_multi_packed_ut = pack_ut == 1 ? 1 : 0;
+            for (int i = 0; i < pack.n; ++i) {  // immediate reductions of the packed weight-gradient jobs
+                const otvae_conv_job& jb = jobs[packed_idx[i]];
+                if (jb.kind != OTVAE_JOB_BWD_WEIGHT || jb.defer_reduce) continue;
+                rc = wgrad_reduce_now(packed_plan[i], jb.wpartial, jb.gw, jb.gb, who, st);
+                if (rc) return rc;
+                ++g_multi_launches;
+            }
         }
         pack = {};
         smem = 0;
         nblocks = 0;
         pack_ut = -1;
-        return OTVAE_OK;
+        return rc;
     };
     for (int i = 0; i < n; ++i) {
         const otvae_conv_job& jb = jobs[i];
-        OTVAE_REQUIRE(jb.kind >= OTVAE_JOB_FWD && jb.kind <= OTVAE_JOB_BWD_WEIGHT, "otvae_conv_multi: job %d: bad kind %d", i,
-                      jb.kind);
-        int rc = check_geom(&jb.geom, "otvae_conv_multi");
+        ConvPlan plan;
+        int rc = conv_plan(&jb.geom, jb.kind, jb.has_bias, who, plan);
         if (rc) return rc;
-        OTVAE_REQUIRE((jb.scale == nullptr) == (jb.shift == nullptr), "otvae_conv_multi: job %d: scale/shift must come together", i);
-        OTVAE_REQUIRE(jb.kind == OTVAE_JOB_FWD || (jb.fold.slots == nullptr && jb.stat_slots == nullptr),
-                      "otvae_conv_multi: job %d: fold / stat_slots belong to forward jobs", i);
-        Geom g = to_geom(&jb.geom);
-        DevJob d = {};
-        d.g = g;
-        d.kind = jb.kind;
-        d.relu = jb.relu;
-        d.scale = jb.scale;
-        d.shift = jb.shift;
-        bool packable = false;
-        const bool ch4 = (g.Cs % 4 == 0) && (g.Cn % 4 == 0);
-        int pcls = PAIR_NONE;  // forward / data-gradient job of the direct or image-tile kernels: may share a launch with its sibling
-        TilePlan tpl = {};
-        dim3 tgrid;
-        size_t tsmem = 0;
-        if (jb.kind == OTVAE_JOB_FWD) {
-            OTVAE_REQUIRE(jb.x && jb.w && jb.y, "otvae_conv_multi: job %d (forward): NULL tensor", i);
-            dim3 grid;
-            fwd_grid(g, d.NT, grid, d.cpad);
-            rc = bn_fold_from_abi("otvae_conv_multi", jb.fold, g.Cs, &d.fold);
-            if (rc) return rc;
-            OTVAE_REQUIRE(!(jb.stat_partial && jb.stat_slots), "otvae_conv_multi: job %d: statistics go to partials OR to slots", i);
-            OTVAE_REQUIRE_SLOTS("otvae_conv_multi (stat_slots)", jb.stat_slots, jb.stat_nslots);
-            OTVAE_REQUIRE(jb.fold.slots == nullptr || g.Cs <= BN_TAB, "otvae_conv_multi: job %d: a folded BatchNorm takes at most %d channels", i, BN_TAB);
-            packable = !conv_small_ok(g) && ch4 && aligned16(jb.x) && aligned16(jb.w) &&
-                       (jb.scale == nullptr || (aligned16(jb.scale) && aligned16(jb.shift))) &&
-                       ((jb.scale == nullptr && jb.fold.slots == nullptr) || g.Cs <= BN_TAB);
-            if (conv_small_ok(g)) {
-                pcls = PAIR_SMALL;
-            } else if (packable && conv_tile_plan(g, 0, tpl, tgrid, tsmem)) {  // image-tile kernel: a launch of its own, or with its sibling
-                packable = false;
-                if (aligned16(jb.y) && (!jb.bias || aligned16(jb.bias)) && (!jb.residual || aligned16(jb.residual))) pcls = PAIR_TILE;
-            }
-            d.a0 = jb.x;
-            d.b0 = jb.w;
-            d.bias = jb.bias;
-            d.res = jb.residual;
-            d.out = jb.y;
-            d.partial = jb.stat_slots ? bn_tag_slots(jb.stat_slots, jb.stat_nslots) : jb.stat_partial;
-            d.gx = grid.x, d.gy = grid.y, d.gz = grid.z;
-        } else if (jb.kind == OTVAE_JOB_BWD_DATA) {
-            OTVAE_REQUIRE(jb.gy && jb.w && jb.gv, "otvae_conv_multi: job %d (data gradient): NULL tensor", i);
-            OTVAE_REQUIRE((jb.mean == nullptr) == (jb.invstd == nullptr), "otvae_conv_multi: job %d: mean/invstd must come together", i);
-            OTVAE_REQUIRE(!(jb.relu || jb.mean) || jb.x, "otvae_conv_multi: job %d: x needed for the ReLU mask / BatchNorm sums", i);
-            OTVAE_REQUIRE(!jb.mean || jb.bn_partial || jb.bn_slots, "otvae_conv_multi: job %d: bn_partial workspace / bn_slots missing", i);
-            OTVAE_REQUIRE(!(jb.bn_partial && jb.bn_slots), "otvae_conv_multi: job %d: BatchNorm-backward sums go to partials OR to slots", i);
-            OTVAE_REQUIRE_SLOTS("otvae_conv_multi (bn_slots)", jb.bn_slots, jb.bn_nslots);
-            dim3 grid;
-            dgrad_grid(g, d.NT, grid, d.cpad);
-            packable = !conv_small_ok(g) && ch4 && aligned16(jb.gy) && aligned16(jb.w);
-            if (conv_small_ok(g)) {
-                pcls = PAIR_SMALL;
-            } else if (packable && conv_tile_plan(g, 1, tpl, tgrid, tsmem)) {  // image-tile kernel: a launch of its own, or with its sibling
-                packable = false;
-                if (aligned16(jb.gv) && (!jb.x || aligned16(jb.x)) && (!jb.scale || (aligned16(jb.scale) && aligned16(jb.shift))) &&
-                    (!jb.mean || (aligned16(jb.mean) && aligned16(jb.invstd))))
-                    pcls = PAIR_TILE;
-            }
-            d.a0 = jb.gy;
-            d.b0 = jb.w;
-            d.xin = jb.x;
-            d.mean = jb.mean;
-            d.invstd = jb.invstd;
-            d.out = jb.gv;
-            d.partial = jb.bn_slots ? bn_tag_slots(jb.bn_slots, jb.bn_nslots) : jb.bn_partial;
-            d.gx = grid.x, d.gy = grid.y, d.gz = grid.z;
-        } else {
-            OTVAE_REQUIRE(jb.x && jb.gy && jb.wpartial && jb.gw, "otvae_conv_multi: job %d (weight gradient): NULL tensor", i);
-            OTVAE_REQUIRE(!jb.has_bias || jb.gb, "otvae_conv_multi: job %d: gb missing", i);
-            int P, nkb, nnb;
-            wgrad_plan(g, jb.has_bias, d.NT, P, d.chunk, nkb, nnb, d.Kp);
-            packable = !conv_small_wgrad_ok(g) && ch4 && aligned16(jb.x) && aligned16(jb.gy) &&
-                       (jb.scale == nullptr || (aligned16(jb.scale) && aligned16(jb.shift)));
-            {
-                WTilePlan wp;
-                int nbk;
-                size_t sm;
-                if (conv_wtile_plan(g, jb.has_bias, wp, nbk, sm)) packable = false;  // image-tile kernel: own launch
-            }
-            d.a0 = jb.x;
-            d.b0 = jb.gy;
-            d.out = jb.wpartial;
-            d.has_bias = jb.has_bias;
-            d.skip_dead = jb.defer_reduce == OTVAE_DEFER_SPARSE;
-            d.gx = nkb, d.gy = nnb, d.gz = P;
-        }
+        rc = check_job(jb, who, i);
+        if (rc) return rc;
+        DevJob d;
+        rc = dev_job(plan, jb, who, d);
+        if (rc) return rc;
+        // packed: an implicit-GEMM job on the vector path; a forward job with a BatchNorm in front only when the LDS table holds its affine
+        const bool packable = plan.route == ROUTE_GEMM && plan.ch4 && gemm_vec_aligned(d) &&
+                              (jb.kind != OTVAE_JOB_FWD || (jb.scale == nullptr && jb.fold.slots == nullptr) || plan.g.Cs <= BN_TAB);
         if (!packable) {
+            // a forward / data-gradient job of the direct kernels, or of the image-tile kernels with every tensor aligned, waits for a
+            // sibling of its class and kind: both in one launch when a two-job kernel exists for them, one by one (as with
+            // OTVAE_PAIR_LAUNCH=0) otherwise
+            int pcls = PAIR_NONE;
+            if (jb.kind != OTVAE_JOB_BWD_WEIGHT) {
+                if (plan.route == ROUTE_DIRECT) pcls = PAIR_SMALL;
+                else if (plan.route == ROUTE_TILE && tile_aligned(plan, d)) pcls = PAIR_TILE;
+            }
             if (pair_on && pcls != PAIR_NONE) {
-                // a job of the direct or image-tile kernels waits for a sibling of its class and kind: both in one launch when a
-                // two-job kernel exists for them, one by one (as with OTVAE_PAIR_LAUNCH=0) otherwise
-                const PairJob cur = {i, pcls, jb.kind, d, tpl, tgrid, tsmem};
-                if (pend.idx >= 0 && pend.cls == cur.cls && pend.kind == cur.kind) {
+                if (pend.idx >= 0 && pend.cls == pcls && pend.plan.kind == jb.kind) {
+                    const PairJob cur = {i, pcls, plan, d};
                     const int pr = launch_pair(pend, cur, st);
                     if (pr == 0) {
                         OTVAE_CHECK_LAUNCH("otvae_conv_multi(pair)");
@@ -2010,15 +1989,15 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
                 }
                 rc = flush_pend();
                 if (rc) return rc;
-                pend = cur;
+                pend = {i, pcls, plan, d};
                 continue;
             }
-            rc = run_single_job(jb, stream);
+            rc = run_single_job(plan, jb, d, st);
             if (rc) return rc;
             continue;
         }
         int job_ut = -1;
-        if (jb.kind != OTVAE_JOB_BWD_WEIGHT) job_ut = ((jb.kind == OTVAE_JOB_FWD ? g.Cs : g.Cn) % KC == 0) ? 1 : 0;
+        if (jb.kind != OTVAE_JOB_BWD_WEIGHT) job_ut = ((jb.kind == OTVAE_JOB_FWD ? plan.g.Cs : plan.g.Cn) % KC == 0) ? 1 : 0;
         if (pack.n == CJ_MAX || (job_ut >= 0 && pack_ut >= 0 && job_ut != pack_ut)) {
             rc = flush();
             if (rc) return rc;
@@ -2029,8 +2008,10 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
         const size_t need = job_smem_bytes(d.kind, d.NT);
         if (need > smem) smem = need;
         packed_idx[pack.n] = i;
+        packed_plan[pack.n] = plan;
         pack.j[pack.n++] = d;
     }
     if (int rc = flush_pend()) return rc;
     return flush();
 }
+
