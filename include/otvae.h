@@ -115,6 +115,12 @@ int otvae_conv_dead_taps(const otvae_conv_geom* g, uint32_t* mask);
 int otvae_wgrad_reduce_batched(int n, const float* const* partial, const int* P, const int* K, const int* Kp,
                                const int* Cn, float* const* gw, float* const* gb, const int* Cs, const uint32_t* dead,
                                void* stream);
+/* The same with a destination window per layer (otvae_conv_job.ldgw / gw_col0; both arrays NULL, or ldgw[j] == 0: dense): gw[j] is
+ * the whole [K][ldgw[j]] gradient, the partials are those of the Cn[j]-wide layer; columns outside the window are written as exact
+ * zeros by the same launch.  A windowed entry has no bias row (Kp[j] == K[j]).  Sums are formed exactly as for the dense layer. */
+int otvae_wgrad_reduce_batched_win(int n, const float* const* partial, const int* P, const int* K, const int* Kp,
+                                   const int* Cn, float* const* gw, float* const* gb, const int* Cs, const uint32_t* dead,
+                                   const int* ldgw, const int* gw_col0, void* stream);
 
 /* ---- several independent ConvLayer kernels in ONE launch ----------------------------------------------------
  * The two branches of a ConvBlock (block[0] and skip read the same x, networks/cnn.py:311-335) in the forward pass,
@@ -192,8 +198,19 @@ typedef struct otvae_conv_job {
     int32_t stat_nslots;        /* slots in use in stat_slots / bn_slots (power of two <= 64) */
     int32_t bn_nslots;
     otvae_bn_fold fold;         /* FWD (fold.slots nullable): the BatchNorm of the INPUT x folded into this launch; scale / shift are then ignored */
+    /* ---- a COLUMN WINDOW of a wider weight (all three 0: the dense layer).  geom.Cn is the width of the window. */
+    int32_t ldw;                /* FWD: row pitch (floats) of the HWIO weight `w` points INTO, >= Cn; `w` is the window's first column.
+                                 * BWD_DATA: the window's rows of the dgrad-layout weight are contiguous, so ldw is 0 or Cs.
+                                 * A job with ldw != 0 always runs as a one-job implicit-GEMM launch (never direct / image-tile / packed). */
+    int32_t ldgw;               /* BWD_WEIGHT: row pitch (floats) of `gw` (the WHOLE gradient, >= gw_col0 + Cn); has_bias must be 0; P from otvae_conv_window_ws.  The */
+    int32_t gw_col0;            /* reduction writes the window's columns [gw_col0, gw_col0 + Cn) and exact zeros into every other column */
 } otvae_conv_job;
 int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream);
+/* The workspace queries for the jobs of a layer over a column window of a weight with `ld` output channels (geom.Cn = the window):
+ * statistics rows / padded Cn of the forward job and BatchNorm-backward rows / padded Cs of the data-gradient job with ldw != 0 (planned
+ * on the implicit GEMM whatever the dense layer of the same geometry takes), and the split-K partials of the weight-gradient job with
+ * ldgw = ld: it splits the pixels as the wide layer's job does, so the window of the gradient is bit for bit what that job computes. */
+int otvae_conv_window_ws(const otvae_conv_geom* g, int ld, int* P_fwd, int* CnPad, int* P_bwd, int* CsPad, int* P_wgrad);
 /* Introspection for measurement (bench.py's per-kernel roofline): what the calling thread's last otvae_conv_multi did --
  * bit i of packed_mask: job i ran inside one packed conv_jobs_kernel launch; uniform_tap: that launch's template flavour
  * (1 = conv_jobs_kernel<true>), -1 if nothing was packed. */

@@ -47,7 +47,8 @@ class ConvJob(C.Structure):  # otvae_conv_job
                 [(n, C.c_void_p) for n in ("x", "scale", "shift", "w", "bias", "residual", "y", "stat_partial", "gy",
                                            "mean", "invstd", "gv", "bn_partial", "wpartial", "gw", "gb", "stat_slots",
                                            "bn_slots")] +
-                [("stat_nslots", C.c_int32), ("bn_nslots", C.c_int32), ("fold", BnFold)])
+                [("stat_nslots", C.c_int32), ("bn_nslots", C.c_int32), ("fold", BnFold)] +
+                [(n, C.c_int32) for n in ("ldw", "ldgw", "gw_col0")])  # column window of a wider weight (0: dense)
 
 
 pj = C.POINTER(ConvJob)
@@ -77,9 +78,11 @@ SIGNATURES = {
     "otvae_conv_bwd_weight_ws": (i32, [pg, i32, pi32]),
     "otvae_conv_bwd_weight": (i32, [pg, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp]),
     "otvae_wgrad_reduce_batched": (i32, [i32, pp, pi32, pi32, pi32, pi32, pp, pp, pi32, pu32, vp]),
+    "otvae_wgrad_reduce_batched_win": (i32, [i32, pp, pi32, pi32, pi32, pi32, pp, pp, pi32, pu32, pi32, pi32, vp]),
     "otvae_conv_dead_taps": (i32, [pg, pu32]),
     "otvae_gmm_diag_energy": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "otvae_conv_multi": (i32, [i32, pj, vp]),
+    "otvae_conv_window_ws": (i32, [pg, i32, pi32, pi32, pi32, pi32, pi32]),
     "otvae_conv_multi_last": (i32, [pu32, pi32]),
     "otvae_conv_multi_launches": (i32, [pi32]),
     "otvae_conv_gemm_chunks": (i32, [pg, i32, pi64, pi64]),

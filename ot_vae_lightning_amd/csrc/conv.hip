@@ -178,7 +178,7 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                                                const float* __restrict__ xin, const float* __restrict__ mean,
                                                const float* __restrict__ invstd, float* __restrict__ gv,
                                                double* __restrict__ partial, int CsPad, int bx, int by, int bz, int gx,
-                                               int gz) {
+                                               int gz, int ldw = 0) {
     using SM = GemmSmem<NT>;
     constexpr int BN = SM::BN;
     constexpr int LDA = SM::LDA;
@@ -201,6 +201,9 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
     const int Hu = g.Hs * g.up, Wu = g.Ws * g.up;
     const int CK = MODE == 0 ? g.Cs : g.Cn;
     const int NC = MODE == 0 ? g.Cn : g.Cs;
+    // row pitch of the B operand: its NC columns may be a window of a wider matrix (ldw > NC; Bmat is the window's first column).
+    // Address arithmetic only; 0 (a compile-time constant in the packed kernels) is the dense matrix.
+    const int LDW = ldw > 0 ? ldw : NC;
     const int n0 = by * BN;
     // source geometry seen by the gather: a tap is in range iff 0 <= t < lim, source coordinate = t >> sh
     const int lim_y = MODE == 0 ? Hu : g.Ho * g.stride, lim_x = MODE == 0 ? Wu : g.Wo * g.stride;
@@ -350,7 +353,7 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                     if (e < 8 * BN && kk < K && n0 + c4 * 4 < NC) {
                         const int t2 = fast_div(kk, inv_ck);
                         const int c2 = kk - t2 * CK;
-                        breg4[j] = *reinterpret_cast<const float4*>(Bmat + ((size_t)tap_w[t2] * CK + c2) * NC + n0 + c4 * 4);
+                        breg4[j] = *reinterpret_cast<const float4*>(Bmat + ((size_t)tap_w[t2] * CK + c2) * LDW + n0 + c4 * 4);
                     }
                 }
                 return;
@@ -387,7 +390,7 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                 if (kk < K && n0 + col < NC) {
                     const int t2 = fast_div(kk, inv_ck);
                     const int c2 = kk - t2 * CK;
-                    v = Bmat[((size_t)tap_w[t2] * CK + c2) * NC + n0 + col];
+                    v = Bmat[((size_t)tap_w[t2] * CK + c2) * LDW + n0 + col];
                 }
                 breg[j] = v;
             }
@@ -479,13 +482,13 @@ __device__ __forceinline__ void conv_gemm_body(char* __restrict__ smem, const Ge
                     ok = u_ok;
 #pragma unroll
                     for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const float4*>(S + (size_t)u_off[i] + c);
-                    const float* brow = Bmat + (size_t)(u_tw + cb) * NC + n0;
+                    const float* brow = Bmat + (size_t)(u_tw + cb) * LDW + n0;
 #pragma unroll
                     for (int j = 0; j < NBV; ++j) {
                         const int e = tid + 256 * j;
                         const int kb = e / (BN / 4), c4 = e - kb * (BN / 4);
                         const bool valid = e < 8 * BN && n0 + c4 * 4 < NC;
-                        b[j] = *reinterpret_cast<const float4*>(valid ? brow + (size_t)kb * NC + c4 * 4 : Bmat);
+                        b[j] = *reinterpret_cast<const float4*>(valid ? brow + (size_t)kb * LDW + c4 * 4 : Bmat);
                         ok |= (valid ? 1 : 0) << (2 + j);
                     }
                 };
@@ -702,16 +705,16 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(Geom g, const float* __r
                                                         const float* __restrict__ res, float* __restrict__ y,
                                                         const float* __restrict__ xin, const float* __restrict__ mean,
                                                         const float* __restrict__ invstd, float* __restrict__ gv,
-                                                        double* __restrict__ partial, int CsPad, BnFold fold) {
+                                                        double* __restrict__ partial, int CsPad, BnFold fold, int ldw) {
     __shared__ __align__(16) char smem[GemmSmem<NT>::bytes];
     if constexpr (TAB) {
         __shared__ __align__(16) float bn_tab[2][BN_TAB];
         bn_tab_fill(fold, scale, shift, g.Cs, bn_tab[0], bn_tab[1], (blockIdx.x | blockIdx.y | blockIdx.z) == 0);
         conv_gemm_body<MODE, NT, VEC, UT, LIVE>(smem, g, S, bn_tab[0], bn_tab[1], relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad,
-                                      blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.z);
+                                      blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.z, ldw);
     } else {
         conv_gemm_body<MODE, NT, VEC, UT, LIVE>(smem, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad,
-                                      blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.z);
+                                      blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.z, ldw);
     }
 }
 
@@ -727,7 +730,8 @@ static inline bool gemm_live_taps() {
 template <int MODE, bool VEC, bool UT, bool LIVE>
 static void launch_gemm_v(int NT, dim3 grid, hipStream_t st, Geom g, const float* S, const float* scale, const float* shift,
                           int relu, const float* Bmat, const float* bias, const float* res, float* y, const float* xin,
-                          const float* mean, const float* invstd, float* gv, double* partial, int CsPad, const BnFold& fold) {
+                          const float* mean, const float* invstd, float* gv, double* partial, int CsPad, const BnFold& fold,
+                          int ldw) {
     // forward launches with a BatchNorm in front (and not more channels than the table holds) take the LDS-table form
     const bool tab = MODE == 0 && (scale != nullptr || fold.slots != nullptr) && g.Cs <= BN_TAB;
 #define OTVAE_CG(N_)                                                                                                        \
@@ -735,12 +739,12 @@ static void launch_gemm_v(int NT, dim3 grid, hipStream_t st, Geom g, const float
         if constexpr (MODE == 0) {                                                                                          \
             if (tab) {                                                                                                      \
                 conv_gemm_kernel<MODE, N_, VEC, UT, LIVE, true><<<grid, 256, 0, st>>>(g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, \
-                                                                            invstd, gv, partial, CsPad, fold);              \
+                                                                            invstd, gv, partial, CsPad, fold, ldw);         \
                 break;                                                                                                      \
             }                                                                                                               \
         }                                                                                                                   \
         conv_gemm_kernel<MODE, N_, VEC, UT, LIVE, false><<<grid, 256, 0, st>>>(g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, \
-                                                                     gv, partial, CsPad, fold);                             \
+                                                                     gv, partial, CsPad, fold, ldw);                        \
     } while (0)
     switch (NT) {
         case 1: OTVAE_CG(1); break;
@@ -756,12 +760,14 @@ static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 template <int MODE>
 static void launch_gemm(int NT, dim3 grid, hipStream_t st, Geom g, const float* S, const float* scale, const float* shift,
                         int relu, const float* Bmat, const float* bias, const float* res, float* y, const float* xin,
-                        const float* mean, const float* invstd, float* gv, double* partial, int CsPad, const BnFold& fold = BnFold{}) {
-    const bool vec = (g.Cs % 4 == 0) && (g.Cn % 4 == 0) && aligned16(S) && aligned16(Bmat) &&
+                        const float* mean, const float* invstd, float* gv, double* partial, int CsPad, const BnFold& fold = BnFold{},
+                        int ldw = 0) {
+    // the 16-byte loads of a weight window need its first column (Bmat) and its row pitch to be multiples of 4 floats
+    const bool vec = (g.Cs % 4 == 0) && (g.Cn % 4 == 0) && aligned16(S) && aligned16(Bmat) && (ldw % 4 == 0) &&
                      (scale == nullptr || (aligned16(scale) && aligned16(shift)));
     const int CK = MODE == 0 ? g.Cs : g.Cn;
 #define OTVAE_LG(V_, U_, L_) \
-    launch_gemm_v<MODE, V_, U_, L_>(NT, grid, st, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad, fold)
+    launch_gemm_v<MODE, V_, U_, L_>(NT, grid, st, g, S, scale, shift, relu, Bmat, bias, res, y, xin, mean, invstd, gv, partial, CsPad, fold, ldw)
     const bool live = vec && gemm_live_taps();
     if (vec && CK % KC == 0) {  // a K-chunk lies inside one tap: uniform-tap pipeline
         if (live) OTVAE_LG(true, true, true);
@@ -1142,18 +1148,35 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(Geom g, const float* __
 // out[e] = sum_p partial[p][e] in a fixed order.
 //   few partials : 4 interleaved p-lanes per element, then p-lane 0..3 through LDS
 //   many partials: one wave per element, lanes stride over p, shuffle tree
+//
+// Destination window (ld > Cn; no bias row then, Kp == K): gw is the [K][ld] gradient of a wider layer and the partials are those of
+// its columns [col0, col0 + Cn).  The loops run over the elements WRITTEN: e -> the partials' element, or none -- a column outside the
+// window, written as an exact zero by this launch.  ld == Cn, col0 == 0 is the dense layer, where the two indices coincide.
+__device__ __forceinline__ bool wgrad_win_src(size_t e, int Cn, int ld, int col0, size_t& src) {
+    src = e;
+    if (ld == Cn) return true;
+    const size_t k = e / (size_t)ld;
+    const int c = (int)(e - k * (size_t)ld) - col0;
+    src = k * (size_t)Cn + (size_t)c;
+    return c >= 0 && c < Cn;
+}
+
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, int P, int K, int Kp, int Cn,
-                                                           float* __restrict__ gw, float* __restrict__ gb) {
+                                                           float* __restrict__ gw, float* __restrict__ gb, int ld, int col0) {
     __shared__ double red[4][64];  // fp32 partials, fp64 sum (see wgrad_reduce_batched_kernel)
-    const size_t total = (size_t)Kp * Cn;
+    const size_t stride = (size_t)Kp * Cn;  // elements per partial
+    const size_t total = (size_t)Kp * ld;   // elements written
+    const bool win = ld != Cn;
     if (P >= 32) {
         const int lane = threadIdx.x & 63;
         for (size_t e = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); e < total; e += (size_t)gridDim.x * 4) {
             double s = 0.0;
-            for (int p = lane; p < P; p += 64) s += (double)partial[(size_t)p * total + e];
+            size_t src;
+            if (wgrad_win_src(e, Cn, ld, col0, src))
+                for (int p = lane; p < P; p += 64) s += (double)partial[(size_t)p * stride + src];
             s = wave_sum(s);
             if (lane == 0) {
-                const int k = e / Cn;
+                const int k = win ? 0 : e / Cn;
                 if (k < K)
                     gw[e] = (float)s;
                 else if (gb)
@@ -1166,13 +1189,14 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     for (size_t e0 = (size_t)blockIdx.x * 64; e0 < total; e0 += (size_t)gridDim.x * 64) {
         const size_t e = e0 + el;
         double s = 0.0;
-        if (e < total)
-            for (int p = pg; p < P; p += 4) s += (double)partial[(size_t)p * total + e];
+        size_t src;
+        if (e < total && wgrad_win_src(e, Cn, ld, col0, src))
+            for (int p = pg; p < P; p += 4) s += (double)partial[(size_t)p * stride + src];
         red[pg][el] = s;
         __syncthreads();
         if (pg == 0 && e < total) {
             const float t = (float)((red[0][el] + red[1][el]) + (red[2][el] + red[3][el]));
-            const int k = e / Cn;
+            const int k = win ? 0 : e / Cn;
             if (k < K)
                 gw[e] = t;
             else if (gb)
@@ -1235,7 +1259,12 @@ struct ConvPlan {
     size_t lds;          // ROUTE_TILE: dynamic LDS bytes
 };
 
-static int conv_plan(const otvae_conv_geom* gg, int kind, int has_bias, const char* who, ConvPlan& p) {
+// pin_gemm: a job over a column window of its weight (otvae_conv_job.ldw != 0) -- only the implicit GEMM takes a row pitch.
+// wide_cn (weight gradient into a window of a wider gradient, otvae_conv_job.ldgw): the pixels are split into the parts the wide layer's
+// plan gives, so every element is summed over the same pixel chunks, in the same order, as in the wide layer's job -- the window of
+// the gradient is bit for bit what the whole layer computes there (the column tiling, NT / nnb, does not enter an element's sum).
+static int conv_plan(const otvae_conv_geom* gg, int kind, int has_bias, const char* who, ConvPlan& p, bool pin_gemm = false,
+                     int wide_cn = 0) {
     OTVAE_REQUIRE(kind >= OTVAE_JOB_FWD && kind <= OTVAE_JOB_BWD_WEIGHT, "%s: bad kind %d", who, kind);
     if (int rc = check_geom(gg, who)) return rc;
     const Geom g = to_geom(gg);
@@ -1255,12 +1284,27 @@ static int conv_plan(const otvae_conv_geom* gg, int kind, int has_bias, const ch
             p.route = conv_small_wgrad_ok(g) ? ROUTE_DIRECT : ROUTE_GEMM;
             p.parts = P;
         }
+        if (wide_cn > g.Cn && p.route == ROUTE_GEMM) {
+            Geom w = g;
+            w.Cn = wide_cn;
+            WTilePlan wt;
+            int wb;
+            size_t wl;
+            if (!conv_small_wgrad_ok(w) && !conv_wtile_plan(w, has_bias, wt, wb, wl)) {  // (the wide layer is on the implicit GEMM too)
+                int nt_, nkb_, nnb_, kp_;
+                wgrad_plan(w, has_bias, nt_, P, p.chunk, nkb_, nnb_, kp_);
+                p.grid.z = P;
+                p.parts = P;
+            }
+        }
         return OTVAE_OK;
     }
     if (kind == OTVAE_JOB_FWD) fwd_grid(g, p.NT, p.grid, p.cpad);
     else dgrad_grid(g, p.NT, p.grid, p.cpad);
     p.parts = p.grid.x * p.grid.z;
-    if (conv_small_ok(g)) {
+    if (pin_gemm) {
+        p.route = ROUTE_GEMM;
+    } else if (conv_small_ok(g)) {
         p.route = ROUTE_DIRECT;
         if (kind == OTVAE_JOB_FWD) p.parts = imin(p.parts, 1024);
     } else if (conv_tile_plan(g, kind, p.tile, p.tgrid, p.lds)) {  // mode 0 / 1 == OTVAE_JOB_FWD / OTVAE_JOB_BWD_DATA
@@ -1289,6 +1333,22 @@ extern "C" int otvae_conv_bwd_data_ws(const otvae_conv_geom* gg, int* P, int* Cs
     return OTVAE_OK;
 }
 
+// the workspace queries for the jobs of a layer over a column window of a weight with `ld` output channels: the forward / data-gradient
+// jobs (otvae_conv_job.ldw != 0) are planned on the implicit GEMM whatever the dense layer of the geometry would take, the
+// weight-gradient job (ldgw = ld) with the wide layer's split-K parts
+extern "C" int otvae_conv_window_ws(const otvae_conv_geom* gg, int ld, int* P_fwd, int* CnPad, int* P_bwd, int* CsPad, int* P_wgrad) {
+    ConvPlan p;
+    if (int rc = conv_plan(gg, OTVAE_JOB_BWD_WEIGHT, 0, "otvae_conv_window_ws", p, false, ld)) return rc;
+    if (P_wgrad) *P_wgrad = p.parts;
+    if (int rc = conv_plan(gg, OTVAE_JOB_FWD, 0, "otvae_conv_window_ws", p, true)) return rc;
+    if (P_fwd) *P_fwd = p.parts;
+    if (CnPad) *CnPad = p.cpad;
+    if (int rc = conv_plan(gg, OTVAE_JOB_BWD_DATA, 0, "otvae_conv_window_ws", p, true)) return rc;
+    if (P_bwd) *P_bwd = p.parts;
+    if (CsPad) *CsPad = p.cpad;
+    return OTVAE_OK;
+}
+
 extern "C" int otvae_conv_bwd_weight_ws(const otvae_conv_geom* gg, int has_bias, int* P) {
     ConvPlan p;
     if (int rc = conv_plan(gg, OTVAE_JOB_BWD_WEIGHT, has_bias, "otvae_conv_bwd_weight_ws", p)) return rc;
@@ -1308,6 +1368,7 @@ struct WrbDesc {
     int P[WRB_MAX], K[WRB_MAX], Kp[WRB_MAX], Cn[WRB_MAX];
     int Cs[WRB_MAX];         // rows per tap (0: no dead-tap information)
     unsigned dead[WRB_MAX];  // bit t: tap t never touches the image, its Cs rows are zero and may be unwritten
+    int ld[WRB_MAX], col0[WRB_MAX];  // destination window (wgrad_win_src): row pitch of gw (== Cn: dense) and the window's first column
 };
 
 __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(WrbDesc d) {
@@ -1319,40 +1380,44 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(WrbDesc d) {
     float* __restrict__ gw = d.gw[l];
     float* __restrict__ gb = d.gb[l];
     const int P = d.P[l], K = d.K[l], Cn = d.Cn[l];
-    const size_t total = (size_t)d.Kp[l] * Cn;
+    const int ld = d.ld[l], col0 = d.col0[l];
+    const bool win = ld != Cn;
+    const size_t stride = (size_t)d.Kp[l] * Cn;  // elements per partial: it (not the window) selects the summation order below
+    const size_t total = (size_t)d.Kp[l] * ld;   // elements written
     const int lane = threadIdx.x & 63;
     const unsigned dead = d.dead[l];
     const int rows_per_tap = d.Cs[l];
-    // element e lies in a row of a dead tap: exactly zero, and the partials may hold garbage there
+    // element e (of the partials) lies in a row of a dead tap: exactly zero, and the partials may hold garbage there
     auto is_dead = [&](size_t e) -> bool {
         if (dead == 0u) return false;
         const int k = (int)(e / (size_t)Cn);
         return k < K && ((dead >> (k / rows_per_tap)) & 1u);
     };
-    if (total >= 4096 && P >= 16) {
+    if (stride >= 4096 && P >= 16) {
         // large gradient: partial rows are far apart (total*4 bytes), so lanes run along e (coalesced 256-byte reads)
         // and the 4 waves split the partials; fixed order: p ascending within a wave, then waves 0..3 through LDS
         const int pg = threadIdx.x >> 6;
         for (size_t e0 = (size_t)blockIdx.x * 64; e0 < total; e0 += (size_t)gridDim.x * 64) {
             const size_t e = e0 + lane;
             double s = 0.0;
-            if (e < total && !is_dead(e)) {
+            size_t src;
+            if (e < total && wgrad_win_src(e, Cn, ld, col0, src) && !is_dead(src)) {
                 int p = pg;
                 for (; p + 12 < P; p += 16) {
-                    const float a0 = partial[(size_t)p * total + e], a1 = partial[(size_t)(p + 4) * total + e];
-                    const float a2 = partial[(size_t)(p + 8) * total + e], a3 = partial[(size_t)(p + 12) * total + e];
+                    const float a0 = partial[(size_t)p * stride + src], a1 = partial[(size_t)(p + 4) * stride + src];
+                    const float a2 = partial[(size_t)(p + 8) * stride + src], a3 = partial[(size_t)(p + 12) * stride + src];
                     s += (double)a0;
                     s += (double)a1;
                     s += (double)a2;
                     s += (double)a3;
                 }
-                for (; p < P; p += 4) s += (double)partial[(size_t)p * total + e];
+                for (; p < P; p += 4) s += (double)partial[(size_t)p * stride + src];
             }
             red[pg][lane] = s;
             __syncthreads();
             if (pg == 0 && e < total) {
                 const float t = (float)((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
-                const int k = e / Cn;
+                const int k = win ? 0 : e / Cn;
                 if (k < K) gw[e] = t;
                 else if (gb) gb[e - (size_t)K * Cn] = t;
             }
@@ -1361,11 +1426,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(WrbDesc d) {
     } else if (P >= 16) {  // small gradient, many partials: one wave per element (neighbouring waves share the lines)
         for (size_t e = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); e < total; e += (size_t)gridDim.x * 4) {
             double s = 0.0;
-            if (!is_dead(e))
-                for (int p = lane; p < P; p += 64) s += (double)partial[(size_t)p * total + e];
+            size_t src;
+            if (wgrad_win_src(e, Cn, ld, col0, src) && !is_dead(src))
+                for (int p = lane; p < P; p += 64) s += (double)partial[(size_t)p * stride + src];
             s = wave_sum(s);
             if (lane == 0) {
-                const int k = e / Cn;
+                const int k = win ? 0 : e / Cn;
                 if (k < K) gw[e] = (float)s;
                 else if (gb) gb[e - (size_t)K * Cn] = (float)s;
             }
@@ -1373,9 +1439,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(WrbDesc d) {
     } else {  // one lane per element, serial over the few partials
         for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
             double s = 0.0;
-            if (!is_dead(e))
-                for (int p = 0; p < P; ++p) s += (double)partial[(size_t)p * total + e];
-            const int k = e / Cn;
+            size_t src;
+            if (wgrad_win_src(e, Cn, ld, col0, src) && !is_dead(src))
+                for (int p = 0; p < P; ++p) s += (double)partial[(size_t)p * stride + src];
+            const int k = win ? 0 : e / Cn;
             if (k < K) gw[e] = (float)s;
             else if (gb) gb[e - (size_t)K * Cn] = (float)s;
         }
@@ -1462,11 +1529,12 @@ extern "C" int otvae_conv_gemm_chunks(const otvae_conv_geom* gg, int mode, int64
     return OTVAE_OK;
 }
 
-extern "C" int otvae_wgrad_reduce_batched(int n, const float* const* partial, const int* P, const int* K, const int* Kp,
-                                          const int* Cn, float* const* gw, float* const* gb, const int* Cs,
-                                          const uint32_t* dead, void* stream) {
+extern "C" int otvae_wgrad_reduce_batched_win(int n, const float* const* partial, const int* P, const int* K, const int* Kp,
+                                              const int* Cn, float* const* gw, float* const* gb, const int* Cs,
+                                              const uint32_t* dead, const int* ldgw, const int* gw_col0, void* stream) {
     OTVAE_REQUIRE(n > 0 && partial && P && K && Kp && Cn && gw && gb, "otvae_wgrad_reduce_batched: bad argument");
     OTVAE_REQUIRE((Cs == nullptr) == (dead == nullptr), "otvae_wgrad_reduce_batched: Cs and dead come together");
+    OTVAE_REQUIRE((ldgw == nullptr) == (gw_col0 == nullptr), "otvae_wgrad_reduce_batched: ldgw and gw_col0 come together");
     hipStream_t st = (hipStream_t)stream;
     for (int base = 0; base < n; base += WRB_MAX) {
         WrbDesc d = {};
@@ -1482,13 +1550,20 @@ extern "C" int otvae_wgrad_reduce_batched(int n, const float* const* partial, co
             d.K[i] = K[j];
             d.Kp[i] = Kp[j];
             d.Cn[i] = Cn[j];
+            d.ld[i] = Cn[j];
+            if (ldgw && ldgw[j]) {  // a column window of a wider gradient: no bias row
+                OTVAE_REQUIRE(Kp[j] == K[j] && gw_col0[j] >= 0 && (int64_t)gw_col0[j] + Cn[j] <= ldgw[j],
+                              "otvae_wgrad_reduce_batched: entry %d: window", j);
+                d.ld[i] = ldgw[j];
+                d.col0[i] = gw_col0[j];
+            }
             if (dead && dead[j]) {
                 OTVAE_REQUIRE(Cs[j] > 0 && K[j] % Cs[j] == 0 && K[j] / Cs[j] <= 32, "otvae_wgrad_reduce_batched: entry %d: Cs", j);
                 d.Cs[i] = Cs[j];
                 d.dead[i] = dead[j];
             }
-            const size_t total = (size_t)Kp[j] * Cn[j];
-            const size_t work = P[j] < 16 ? cdiv(total, 256) : (total >= 4096 ? cdiv(total, 64) : cdiv(total, 4));
+            const size_t stride = (size_t)Kp[j] * Cn[j], total = (size_t)Kp[j] * d.ld[i];  // (the kernel's branch test; elements written)
+            const size_t work = P[j] < 16 ? cdiv(total, 256) : (stride >= 4096 ? cdiv(total, 64) : cdiv(total, 4));
             if (work > maxwork) maxwork = work;
         }
         dim3 grid(imin((int)maxwork, 512), m);
@@ -1496,6 +1571,12 @@ extern "C" int otvae_wgrad_reduce_batched(int n, const float* const* partial, co
         OTVAE_CHECK_LAUNCH("otvae_wgrad_reduce_batched");
     }
     return OTVAE_OK;
+}
+
+extern "C" int otvae_wgrad_reduce_batched(int n, const float* const* partial, const int* P, const int* K, const int* Kp,
+                                          const int* Cn, float* const* gw, float* const* gb, const int* Cs,
+                                          const uint32_t* dead, void* stream) {
+    return otvae_wgrad_reduce_batched_win(n, partial, P, K, Kp, Cn, gw, gb, Cs, dead, nullptr, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ multi-job launch
@@ -1623,9 +1704,12 @@ static int check_job(const otvae_conv_job& jb, const char* who, int index) {
     JOB_REQUIRE((jb.scale == nullptr) == (jb.shift == nullptr), "scale and shift must be given together");
     JOB_REQUIRE(jb.kind == OTVAE_JOB_FWD || (jb.fold.slots == nullptr && jb.stat_slots == nullptr),
                 "fold / stat_slots belong to forward jobs");
+    JOB_REQUIRE(jb.kind == OTVAE_JOB_BWD_WEIGHT ? jb.ldw == 0 : (jb.ldgw == 0 && jb.gw_col0 == 0),
+                "ldw belongs to forward / data-gradient jobs, ldgw / gw_col0 to weight-gradient jobs");
     switch (jb.kind) {
         case OTVAE_JOB_FWD:
             JOB_REQUIRE(jb.x && jb.w && jb.y, "NULL tensor");
+            JOB_REQUIRE(jb.ldw == 0 || jb.ldw >= jb.geom.Cn, "ldw: the row pitch of a weight window is at least Cn");
             JOB_REQUIRE(!(jb.stat_partial && jb.stat_slots), "statistics go to partials OR to slots");
             JOB_REQUIRE(!jb.stat_slots || (aligned16(jb.stat_slots) && bn_slots_ok(jb.stat_nslots)), slots_rule);
             JOB_REQUIRE(jb.fold.slots == nullptr || jb.geom.Cs <= BN_TAB,
@@ -1633,6 +1717,7 @@ static int check_job(const otvae_conv_job& jb, const char* who, int index) {
             return OTVAE_OK;
         case OTVAE_JOB_BWD_DATA:
             JOB_REQUIRE(jb.gy && jb.w && jb.gv, "NULL tensor");
+            JOB_REQUIRE(jb.ldw == 0 || jb.ldw == jb.geom.Cs, "ldw: the rows of a dgrad-layout weight window are contiguous (0 or Cs)");
             JOB_REQUIRE((jb.mean == nullptr) == (jb.invstd == nullptr), "mean and invstd must be given together");
             JOB_REQUIRE(!(jb.relu || jb.mean) || jb.x, "x needed for the ReLU mask / BatchNorm sums");
             JOB_REQUIRE(!jb.mean || jb.bn_partial || jb.bn_slots, "bn_partial workspace / bn_slots missing");
@@ -1642,6 +1727,9 @@ static int check_job(const otvae_conv_job& jb, const char* who, int index) {
         default:
             JOB_REQUIRE(jb.x && jb.gy && jb.wpartial && jb.gw, "NULL tensor");
             JOB_REQUIRE(!jb.has_bias || jb.gb, "gb missing");
+            JOB_REQUIRE(jb.ldgw == 0 ? jb.gw_col0 == 0
+                                     : (!jb.has_bias && jb.gw_col0 >= 0 && (int64_t)jb.gw_col0 + jb.geom.Cn <= jb.ldgw),
+                        "ldgw / gw_col0: a gradient window has no bias and lies inside the row pitch");
             return OTVAE_OK;
     }
 }
@@ -1707,15 +1795,19 @@ static bool gemm_vec_aligned(const DevJob& d) {
 }
 
 // the immediate split-K reduction of a weight-gradient job: partial[parts][Kp][Cn] -> gw (+ gb)
-static int wgrad_reduce_now(const ConvPlan& p, const float* partial, float* gw, float* gb, const char* who, hipStream_t st) {
+// (jb.ldgw != 0: into the column window of the wider gradient gw, zeros around it)
+static int wgrad_reduce_now(const ConvPlan& p, const otvae_conv_job& jb, const char* who, hipStream_t st) {
     const int P = p.parts, Kp = p.Kp;
-    const size_t total = (size_t)Kp * p.g.Cn;
-    wgrad_reduce_kernel<<<imin(cdiv(total, P >= 32 ? 4 : 64), 2048), 256, 0, st>>>(partial, P, Kp - (p.has_bias ? 1 : 0), Kp, p.g.Cn, gw, gb);
+    const int ld = jb.ldgw ? jb.ldgw : p.g.Cn;
+    const size_t total = (size_t)Kp * ld;  // elements written
+    wgrad_reduce_kernel<<<imin(cdiv(total, P >= 32 ? 4 : 64), 2048), 256, 0, st>>>(jb.wpartial, P, Kp - (p.has_bias ? 1 : 0), Kp, p.g.Cn, jb.gw,
+                                                                                   jb.gb, ld, jb.gw_col0);
     OTVAE_CHECK_LAUNCH(who);
     return OTVAE_OK;
 }
 
-// One job, on the route and with the grid of its plan.  d = dev_job(p, jb); jb itself is read for the weight gradient's reduction only.
+// One job, on the route and with the grid of its plan.  d = dev_job(p, jb); jb itself is read for the weight gradient's reduction and the
+// forward job's weight pitch only (neither is part of the packed kernels' job table).
 // An image-tile launch refuses misaligned tensors, and hands a refused LDS grant (OTVAE_ELAUNCH, error text set) up as it is.
 static int launch_planned(const ConvPlan& p, const otvae_conv_job& jb, const DevJob& d, const char* who, hipStream_t st) {
     const Geom& g = p.g;
@@ -1735,7 +1827,7 @@ static int launch_planned(const ConvPlan& p, const otvae_conv_job& jb, const Dev
             OTVAE_REQUIRE(rc == 0, "%s: no image-tile kernel for nt=%d rbw=%d", who, p.tile.nt, p.tile.rbw);
         } else if (fwd) {
             launch_gemm<0>(p.NT, p.grid, st, g, d.a0, d.scale, d.shift, d.relu, d.b0, d.bias, d.res, d.out, nullptr, nullptr, nullptr, nullptr,
-                           d.partial, p.cpad, d.fold);
+                           d.partial, p.cpad, d.fold, jb.ldw);
         } else {
             launch_gemm<1>(p.NT, p.grid, st, g, d.a0, d.scale, d.shift, d.relu, d.b0, nullptr, nullptr, nullptr, d.xin, d.mean, d.invstd, d.out,
                            d.partial, p.cpad);
@@ -1775,13 +1867,13 @@ static int launch_planned(const ConvPlan& p, const otvae_conv_job& jb, const Dev
 #undef OTVAE_WG
     }
     OTVAE_CHECK_LAUNCH(who);
-    return defer_reduce ? OTVAE_OK : wgrad_reduce_now(p, partial, jb.gw, jb.gb, who, st);
+    return defer_reduce ? OTVAE_OK : wgrad_reduce_now(p, jb, who, st);
 }
 
 // the one-job entry points: plan, check, launch
 static int run_one_job(const otvae_conv_geom* gg, otvae_conv_job& jb, const char* who, void* stream) {
     ConvPlan p;
-    if (int rc = conv_plan(gg, jb.kind, jb.has_bias, who, p)) return rc;  // (refuses a NULL geometry)
+    if (int rc = conv_plan(gg, jb.kind, jb.has_bias, who, p, jb.ldw != 0, jb.ldgw)) return rc;  // (refuses a NULL geometry)
     jb.geom = *gg;
     if (int rc = check_job(jb, who, -1)) return rc;
     DevJob d;
@@ -1942,7 +2034,7 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
             for (int i = 0; i < pack.n; ++i) {  // immediate reductions of the packed weight-gradient jobs
                 const otvae_conv_job& jb = jobs[packed_idx[i]];
                 if (jb.kind != OTVAE_JOB_BWD_WEIGHT || jb.defer_reduce) continue;
-                rc = wgrad_reduce_now(packed_plan[i], jb.wpartial, jb.gw, jb.gb, who, st);
+                rc = wgrad_reduce_now(packed_plan[i], jb, who, st);
                 if (rc) return rc;
                 ++g_multi_launches;
             }
@@ -1956,15 +2048,16 @@ extern "C" int otvae_conv_multi(int n, const otvae_conv_job* jobs, void* stream)
     for (int i = 0; i < n; ++i) {
         const otvae_conv_job& jb = jobs[i];
         ConvPlan plan;
-        int rc = conv_plan(&jb.geom, jb.kind, jb.has_bias, who, plan);
+        int rc = conv_plan(&jb.geom, jb.kind, jb.has_bias, who, plan, jb.ldw != 0, jb.ldgw);
         if (rc) return rc;
         rc = check_job(jb, who, i);
         if (rc) return rc;
         DevJob d;
         rc = dev_job(plan, jb, who, d);
         if (rc) return rc;
-        // packed: an implicit-GEMM job on the vector path; a forward job with a BatchNorm in front only when the LDS table holds its affine
-        const bool packable = plan.route == ROUTE_GEMM && plan.ch4 && gemm_vec_aligned(d) &&
+        // packed: an implicit-GEMM job on the vector path; a forward job with a BatchNorm in front only when the LDS table holds its affine;
+        // never a job over a weight window (the packed kernels' job table carries no pitch)
+        const bool packable = plan.route == ROUTE_GEMM && plan.ch4 && gemm_vec_aligned(d) && jb.ldw == 0 &&
                               (jb.kind != OTVAE_JOB_FWD || (jb.scale == nullptr && jb.fold.slots == nullptr) || plan.g.Cs <= BN_TAB);
         if (!packable) {
             // a forward / data-gradient job of the direct kernels, or of the image-tile kernels with every tensor aligned, waits for a

@@ -88,12 +88,12 @@ def _geom(x: Tensor, weight: Tensor, stride: int, pad: int, up: int) -> Tuple[Co
 _PLAN_CACHE: dict = {}
 
 
-def _conv_plan(g: ConvGeom, has_bias: bool):
+def _conv_plan(g: ConvGeom, has_bias: bool, window: int = 0):
     """Workspace shapes the library wants for this geometry -- (forward statistics partials, their row length, weight-gradient
     partials, data-gradient BatchNorm partials, their row length, dead-tap mask) -- asked once per geometry: four C calls per
-    layer and pass otherwise, on a host-bound eagerly issued step."""
+    layer and pass otherwise, on a host-bound eagerly issued step.  ``window``: for jobs over a column window of a weight with that many output channels (ConvSpec.window)."""
     env = os.environ  # the kernel-selection switches (DESIGN.md section 4) are read per call by the library and change the plan
-    key = (g.N, g.Hs, g.Ws, g.Cs, g.up, g.Ho, g.Wo, g.Cn, g.KH, g.KW, g.stride, g.pad, has_bias,
+    key = (g.N, g.Hs, g.Ws, g.Cs, g.up, g.Ho, g.Wo, g.Cn, g.KH, g.KW, g.stride, g.pad, has_bias, window,
            "OTVAE_NO_TILE" in env, "OTVAE_NO_WTILE" in env, "OTVAE_TILE_ALL" in env, "OTVAE_WTILE_ALL" in env)
     plan = _PLAN_CACHE.get(key)
     if plan is None:
@@ -103,6 +103,9 @@ def _conv_plan(g: ConvGeom, has_bias: bool):
         check(lib.otvae_conv_bwd_weight_ws(C.byref(g), int(has_bias), C.byref(p_w)), "otvae_conv_bwd_weight_ws")
         check(lib.otvae_conv_bwd_data_ws(C.byref(g), C.byref(p_d), C.byref(cp)), "otvae_conv_bwd_data_ws")
         check(lib.otvae_conv_dead_taps(C.byref(g), C.byref(dead)), "otvae_conv_dead_taps")
+        if window:
+            check(lib.otvae_conv_window_ws(C.byref(g), window, C.byref(p_s), C.byref(ld), C.byref(p_d), C.byref(cp), C.byref(p_w)),
+                  "otvae_conv_window_ws")
         plan = _PLAN_CACHE[key] = (p_s.value, ld.value, p_w.value, p_d.value, cp.value, dead.value)
     return plan
 
@@ -470,11 +473,11 @@ class _PendingReduce:
             _PendingReduce._reduced[device] = len(st)
 
     @staticmethod
-    def add(device, partial, p, k, kp, cn, gw, gb, cs, dead):
+    def add(device, partial, p, k, kp, cn, gw, gb, cs, dead, ldgw=0, col0=0):
         st = _PendingReduce._state.setdefault(device, [])
         if not st:
             torch.autograd.Variable._execution_engine.queue_callback(lambda dev=device: _PendingReduce.flush(dev))
-        st.append((partial, p, k, kp, cn, gw, gb, cs, dead))
+        st.append((partial, p, k, kp, cn, gw, gb, cs, dead, ldgw, col0))
 
     @staticmethod
     def reset(device) -> None:
@@ -506,10 +509,11 @@ class _PendingReduce:
                 arr[i] = v
             return arr
 
-        check(lib.otvae_wgrad_reduce_batched(n, ptr_array([e[0] for e in entries]), ia(1), ia(2), ia(3), ia(4),
-                                             raw([e[5] for e in entries]), raw([e[6] for e in entries]), ia(7),
-                                             (C.c_uint32 * n)(*[e[8] for e in entries]), stream_ptr),
-              "otvae_wgrad_reduce_batched")
+        # (ldgw, gw_col0: the entries whose gw is a wider gradient that receives a column window, zeros around it)
+        check(lib.otvae_wgrad_reduce_batched_win(n, ptr_array([e[0] for e in entries]), ia(1), ia(2), ia(3), ia(4),
+                                                 raw([e[5] for e in entries]), raw([e[6] for e in entries]), ia(7),
+                                                 (C.c_uint32 * n)(*[e[8] for e in entries]), ia(9), ia(10), stream_ptr),
+              "otvae_wgrad_reduce_batched_win")
 
     @staticmethod
     def flush(device):
@@ -640,12 +644,15 @@ class PriorLane:
 # ------------------------------------------------------------------------------------------------ fused ConvLayer(s)
 class ConvSpec:
     """Static description of one ConvLayer branch (everything that is not a tensor)."""
-    __slots__ = ("stride", "pad", "up", "relu", "has_norm", "has_bias", "has_residual", "out_stats")
+    __slots__ = ("stride", "pad", "up", "relu", "has_norm", "has_bias", "has_residual", "out_stats", "window")
 
-    def __init__(self, stride, pad, up, relu, has_norm, has_bias, has_residual=False, out_stats=False):
+    def __init__(self, stride, pad, up, relu, has_norm, has_bias, has_residual=False, out_stats=False, window=None):
         self.stride, self.pad, self.up, self.relu = stride, pad, up, relu
         self.has_norm, self.has_bias, self.has_residual = has_norm, has_bias, has_residual
         self.out_stats = out_stats  # also emit per-channel partial sums of the output (next layer's BatchNorm)
+        # (col0, ld): the branch's weight tensor is the view [col0: col0 + Cn] of a wider bias-free 1x1 HWIO parameter with ld output
+        # channels (params_ref holds that parameter): the layer computes those columns only (otvae_conv_job.ldw / ldgw / gw_col0)
+        self.window = window
 
 
 class _ConvBNFn(torch.autograd.Function):
@@ -708,7 +715,7 @@ def conv_forward_launch(x, specs, stats, tensors):
         y = empty_nhwc(x.shape[0], w.shape[0], ho, wo, x)
         part, st, slots_out = None, None, None
         if sp.out_stats:
-            p_s, ld = _conv_plan(g, bias is not None)[:2]
+            p_s, ld = _conv_plan(g, bias is not None, sp.window[1] if sp.window is not None else 0)[:2]
             slots_out = SlotArena.take(x.device, ld, p_s)
             if slots_out is not None:
                 st = slots_out
@@ -725,6 +732,8 @@ def conv_forward_launch(x, specs, stats, tensors):
             jb.shift = ptr(shifts[b]) if sp.has_norm else None
         jn += 1 if sp.has_norm else 0
         jb.w, jb.bias, jb.residual, jb.y, jb.stat_partial = ptr(w), ptr(bias), ptr(res), ptr(y), ptr(part)
+        if sp.window is not None:
+            jb.ldw = sp.window[1]   # (w is the view: its data pointer is the window's first column)
         if slots_out is not None:
             jb.stat_slots, jb.stat_nslots = ptr(slots_out.buf), slots_out.n
         keep.append(part)
@@ -778,10 +787,12 @@ def conv_backward_launch(x, tensors, specs, geoms, stats, params_ref, gys, need_
         gy = as_nhwc(gy)
         g = geoms[b]
         # --- weight / bias gradient
-        _, _, p_w, p_d, cp, dead_taps = _conv_plan(g, sp.has_bias)
+        _, _, p_w, p_d, cp, dead_taps = _conv_plan(g, sp.has_bias, sp.window[1] if sp.window is not None else 0)
         kk = g.KH * g.KW * g.Cs + (1 if sp.has_bias else 0)
         wpart = torch.empty((p_w, kk, g.Cn), device=x.device, dtype=torch.float32)
-        gw = _grad_buffer(pw, w)
+        col0, ldgw = sp.window if sp.window is not None else (0, 0)
+        # (a window: the gradient of the whole parameter; the job's partials cover the window, the reduction writes zeros around it)
+        gw = _grad_buffer(pw, w if sp.window is None else pw)
         gb = _grad_buffer(pb, bias) if sp.has_bias else None
         defer = (pw is not None and getattr(pw, "_otvae_grad_view", None) is not None and
                  (not sp.has_bias or getattr(pb, "_otvae_grad_view", None) is not None))
@@ -796,10 +807,12 @@ def conv_backward_launch(x, tensors, specs, geoms, stats, params_ref, gys, need_
         jb.scale = ptr(scales[b]) if sp.has_norm else None
         jb.shift = ptr(shifts[b]) if sp.has_norm else None
         jb.wpartial, jb.gw, jb.gb = ptr(wpart), ptr(gw), ptr(gb)
+        jb.ldgw, jb.gw_col0 = ldgw, col0
         keep += [wpart, gy, scales[b] if sp.has_norm else None, shifts[b] if sp.has_norm else None]
         if defer:
             _PendingReduce.add(x.device, wpart, p_w, kk - (1 if sp.has_bias else 0), kk, g.Cn,
-                               gw.data_ptr(), gb.data_ptr() if gb is not None else None, g.Cs, 0 if _DENSE_REDUCE else dead_taps)
+                               gw.data_ptr(), gb.data_ptr() if gb is not None else None, g.Cs, 0 if _DENSE_REDUCE else dead_taps,
+                               ldgw, col0)
         # --- data gradient (needed for dx and for the BatchNorm parameter gradients)
         gv = None
         part = None    # the BatchNorm-backward sums of this branch: fp64 partials (Tensor) or statistic slots (Slots)
@@ -812,9 +825,12 @@ def conv_backward_launch(x, tensors, specs, geoms, stats, params_ref, gys, need_
         elif need_dx or sp.has_norm:
             wd = getattr(pw, "_otvae_wd", None) if pw is not None else None
             if wd is None:
-                wd = torch.empty(g.KH * g.KW * g.Cn * g.Cs, device=x.device, dtype=torch.float32)
-                check(lib.otvae_weight_transpose(ptr(w), ptr(wd), g.KH * g.KW, g.Cs, g.Cn, stream()),
+                wcols = ldgw or g.Cn
+                wd = torch.empty(g.KH * g.KW * wcols * g.Cs, device=x.device, dtype=torch.float32)
+                check(lib.otvae_weight_transpose(ptr(w if sp.window is None else pw), ptr(wd), g.KH * g.KW, g.Cs, wcols, stream()),
                       "otvae_weight_transpose")
+            if sp.window is not None:
+                wd = wd[col0 * g.Cs: (col0 + g.Cn) * g.Cs]   # [ld][Cs] for a 1x1 layer: the window's rows are contiguous
             gv = empty_nhwc(n, cs, hs, ws, x)
             if sp.has_norm:
                 # slots only when every normalised branch of this call gets them (one consumer launch reads them all)
@@ -836,6 +852,8 @@ def conv_backward_launch(x, tensors, specs, geoms, stats, params_ref, gys, need_
             nd += 1
             jb.kind, jb.relu, jb.geom = _lib.JOB_BWD_DATA, int(sp.relu), g
             jb.gy, jb.w, jb.x = ptr(gy), ptr(wd), ptr(x)
+            if sp.window is not None:
+                jb.ldw = g.Cs   # keeps the job on the route _conv_plan(window=True) sized its workspace for
             jb.scale = ptr(scales[b]) if sp.has_norm else None
             jb.shift = ptr(shifts[b]) if sp.has_norm else None
             jb.mean = ptr(mean) if sp.has_norm else None
@@ -1544,6 +1562,98 @@ def attention_stage(x: Tensor, qkv_branch: dict, n_heads: int, proj_branch: dict
             need_aux, stats_out)
     y = _AttnStageFn.apply(x, meta, wq, qkv_branch.get("gamma"), qkv_branch.get("beta"), wp, res)
     if stats_out:
+        y._otvae_stats = stats_out[0]
+    return y
+
+
+# OTVAE_ATTN_ONE_TOKEN=0 (A/B switch): an AttentionBlock on a one-pixel map runs its three launches (qkv convolution, one-token
+# attention, output projection) instead of the value projection alone
+ATTN_ONE_TOKEN = os.environ.get("OTVAE_ATTN_ONE_TOKEN", "1") != "0"
+
+
+# Python-side state of the ``otvae::qkv_attention_one_token`` call in flight, which an operator schema cannot carry: (BatchNorm stats
+# tuple with the pending fold, parameter objects of the two projections -- they own the trainer's flat gradient slots --, whether the
+# output's statistics are wanted, the list that receives them).  Set by ``attention_one_token`` around the call; the operator's
+# autograd context keeps it for the backward pass.
+_ONE_TOKEN_CALL: Optional[tuple] = None
+
+
+def _one_token_specs(c: int, has_norm: bool, has_res: bool, out_stats: bool):
+    return (ConvSpec(1, 0, 1, False, has_norm, False, False, False, window=(2 * c, 3 * c)),
+            ConvSpec(1, 0, 1, False, False, False, has_res, out_stats))
+
+
+def one_token_forward(x, wq, gamma, beta, wp, res, call):
+    """(y, v) of ``otvae::qkv_attention_one_token`` (ops.py): y = proj_out(Wv . BN(x)) [+ residual], the AttentionBlock on a one-pixel
+    map.  With one key the softmax weight is 1, so the attention returns v, dq = dk = 0 and dv = gout: the query and key columns of
+    qkv.weight enter neither y nor dx, and their gradient is exactly zero.  Two convolution jobs each way, the first over the column
+    window [2C, 3C) of the [C][3C] weight."""
+    if call is None:
+        raise RuntimeError("otvae::qkv_attention_one_token is called through functional.attention_one_token")
+    stats, _, _, out_stats, stats_out = call
+    c = x.shape[1]
+    sp_v, sp_p = _one_token_specs(c, gamma is not None, res is not None, out_stats)
+    no_stats = (None, None, [None], [None], stats[4])
+    (v,), _, _ = conv_forward_launch(x, (sp_v,), stats, (wq[2 * c:], None, gamma, beta, None))
+    (y,), _, st = conv_forward_launch(v, (sp_p,), no_stats, (wp, None, None, None, res))
+    stats_out.extend(st)
+    return y, v
+
+
+def one_token_backward(call, need_dx, gy, x, wq, gamma, beta, wp, res, v):
+    """gradients of (x, wq, gamma, beta, wp, residual): the projection's data and weight gradient, then the v-window data gradient
+    and the v-window weight-gradient job, through ``conv_backward_launch`` (side-stream forks, deferred reduction, BatchNorm pair)"""
+    stats, pref_q, pref_p, _, _ = call
+    c = x.shape[1]
+    sp_v, sp_p = _one_token_specs(c, gamma is not None, res is not None, False)
+    no_stats = (None, None, [None], [None], stats[4])
+    wv = wq[2 * c:]
+    geom_v, geom_p = _geom(x, wv, 1, 0, 1)[0], _geom(v, wp, 1, 0, 1)[0]
+    gout, per_p = conv_backward_launch(v, (wp, None, None, None, res), (sp_p,), (geom_p,), no_stats, (pref_p,), (gy,), True)
+    dx, per_v = conv_backward_launch(x, (wv, None, gamma, beta, None), (sp_v,), (geom_v,), stats, (pref_q,), (gout,), need_dx)
+    return dx, per_v[0][0], per_v[0][2], per_v[0][3], per_p[0][0], per_p[0][4]
+
+
+def attention_one_token(x: Tensor, qkv_branch: dict, n_heads: int, proj_branch: dict, training: bool = True) -> Optional[Tensor]:
+    """The reference's AttentionBlock (networks/cnn.py:212-240) on a one-pixel map as the value projection and the output projection
+    alone (``otvae::qkv_attention_one_token``), or None when this is not such a block: H * W == 1, both 1x1 convolutions plain (``_plain_1x1``: no
+    bias, activation, FiLM, equalized learning rate, groups, dilation, group norm).  The caller checks that the attention module is
+    the package's QKVAttention."""
+    if not ATTN_ONE_TOKEN or x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda:
+        return None
+    n, hc, hh, ww = x.shape
+    if hh * ww != 1 or n_heads <= 0 or hc % n_heads != 0:
+        return None  # (a width the heads do not divide: the three-launch path raises the reference's error)
+    if not (_plain_1x1(qkv_branch, 3 * hc, hc) and _plain_1x1(proj_branch, hc, hc)):
+        return None
+    if proj_branch.get("gamma") is not None or qkv_branch.get("residual") is not None or qkv_branch.get("generic") \
+            or proj_branch.get("generic"):
+        return None
+    x = as_nhwc(x)
+    res = proj_branch.get("residual")
+    if res is not None:
+        res = as_nhwc(res)
+    wq, wp = qkv_branch["weight"], proj_branch["weight"]
+    gamma, beta = qkv_branch.get("gamma"), qkv_branch.get("beta")
+    mean = invstd = fold = None
+    scales, shifts = [None], [None]
+    if gamma is not None:
+        bn = BNBranch(gamma, beta, qkv_branch.get("running_mean"), qkv_branch.get("running_var"), qkv_branch.get("num_batches_tracked"))
+        if training:
+            mean, invstd, scales, shifts, fold = bn_batch_stats(x, [bn], allow_fold=True)
+        else:
+            mean, invstd, s0, h0 = bn_eval_affine(bn)
+            scales, shifts = [s0], [h0]
+    stats = (mean, invstd, scales, shifts, training, fold)
+    stats_out: list = []
+    global _ONE_TOKEN_CALL
+    _ONE_TOKEN_CALL = (stats, (wq, None, gamma, beta), (wp, None, None, None), bool(proj_branch.get("out_stats", False)) and training,
+                       stats_out)
+    try:
+        y, _ = torch.ops.otvae.qkv_attention_one_token(x, wq, gamma, beta, wp, res)
+    finally:
+        _ONE_TOKEN_CALL = None
+    if stats_out and stats_out[0] is not None:
         y._otvae_stats = stats_out[0]
     return y
 

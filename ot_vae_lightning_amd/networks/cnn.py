@@ -254,6 +254,10 @@ class AttentionBlock(nn.Module):
 
     def forward(self, x: Tensor, embed: Optional[Tensor] = None, *, residual: Optional[Tensor] = None) -> Tensor:
         qb, pb = self.qkv.branch(None, False, embed), self.proj_out.branch(residual, True)
+        if type(self.attention) is QKVAttention:   # one-pixel map: attention over one token returns v, only its projection runs
+            y = HF.attention_one_token(x, qb, self.attention.n_heads, pb, training=self.qkv.training)
+            if y is not None:
+                return y
         y = HF.attention_stage(x, qb, self.attention.n_heads, pb, training=self.qkv.training)   # one launch where the shapes allow
         if y is not None:
             return y

@@ -4,6 +4,8 @@ that an unmodified ``training_step`` / ``loss.backward()`` runs them, the profil
 with known output shapes.  Every forward op has a ``*_backward`` op of its own; nothing here computes outside the HIP library.
 
     otvae::qkv_attention            QKVAttention.forward                         networks/nets_utils.py:63-82
+    otvae::qkv_attention_one_token  AttentionBlock.forward on a one-pixel map    networks/cnn.py:212-240
+                                    (one token: the attention returns v)
     otvae::bn_batch_stats +         ConvLayer.forward (BN -> act -> up -> conv)  networks/cnn.py:183-192
     otvae::conv_bn_act
     otvae::gaussian_prior           GaussianPrior.encode (+ loss coefficient)    prior/gaussian.py:63-96, prior/base.py:74-78
@@ -139,6 +141,40 @@ def _attn_backward(ctx, gout, _glse, _gaux):
 
 
 torch.library.register_autograd("otvae::qkv_attention", _attn_backward, setup_context=_attn_setup)
+
+
+# ---- attention over ONE token (the AttentionBlock on a one-pixel map): the attention returns v, so the operator is the block's value
+# projection and output projection (functional.one_token_forward / one_token_backward).  Its backward writes parameter gradients
+# into the training engine's flat slots like functional.conv_layers does, so it is a Python formula and not a ``*_backward`` op.
+def _attn_one_token_fwd(x: Tensor, wq: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], wp: Tensor, residual: Optional[Tensor]):
+    from . import functional as HF
+    return HF.one_token_forward(x, wq, gamma, beta, wp, residual, HF._ONE_TOKEN_CALL)
+
+
+def _attn_one_token_fake(x, wq, gamma, beta, wp, residual):
+    n, c, h, w = x.shape
+    return _nhwc(n, c, h, w, x), _nhwc(n, c, h, w, x)
+
+
+_define("qkv_attention_one_token", "(Tensor x, Tensor wq, Tensor? gamma, Tensor? beta, Tensor wp, Tensor? residual) -> (Tensor, Tensor)",
+        _attn_one_token_fwd, _attn_one_token_fake)
+
+
+def _attn_one_token_setup(ctx, inputs, output):
+    from . import functional as HF
+    ctx.save_for_backward(*inputs, output[1])
+    ctx.call = HF._ONE_TOKEN_CALL
+    ctx.set_materialize_grads(False)  # v is the block's inner tensor: nothing reads it outside
+
+
+def _attn_one_token_backward(ctx, gy, _gv):
+    if gy is None:
+        return None, None, None, None, None, None
+    from . import functional as HF
+    return HF.one_token_backward(ctx.call, ctx.needs_input_grad[0], gy, *ctx.saved_tensors)
+
+
+torch.library.register_autograd("otvae::qkv_attention_one_token", _attn_one_token_backward, setup_context=_attn_one_token_setup)
 
 
 # ------------------------------------------------------------------------------------------------ ConvLayer
