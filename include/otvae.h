@@ -581,6 +581,34 @@ int otvae_sqdist_max(int dtype, const void* x, const void* y, int nb, int N, int
 int otvae_ot_cost_grad(int dtype, const void* z, const void* y, const void* pi, const void* g, int ng, double scale,
                        const void* gadd, int N, int M, int D, void* gz, void* stream);
 
+/* ---- Sinkhorn divergence between latents and prior draws (SinkhornDivergencePrior; Genevay, Peyre, Cuturi 2018) -------- */
+/* z[N][D], y[M][D], dtype 0 = fp32 / 1 = fp64, N, M, D >= 1, N and M may differ.
+ *   S(z, y) = W(z, y) - W(z, z) / 2 - W(y, y) / 2,   W(p, q) = sum_ij C_pq,ij pi_pq,ij,   C_pq,ij = |p_i - q_j|^2
+ * cmax = max C_zy; the three plans are the entropic plans of C_zy / cmax, C_zz / cmax, C_yy / cmax with uniform marginals after exactly
+ * max_iter iterations of sinkhorn_log (v, then u) with the same reg: one absolute epsilon = reg cmax for all three, the same iteration
+ * count for all three (no threshold), so that the bias terms cancel and S(z, z) = 0.
+ * One cost launch leaves all three matrices: the cross block with the arithmetic and the tile maxima of otvae_sqdist_max (fp32: 64 x 64
+ * tiles on the 16 x 16 x 4 MFMA path), the self blocks from their upper-triangle tiles mirrored at the store: bitwise symmetric, exact
+ * zero diagonal.  The solve is otvae_sinkhorn_log_normalized's, every problem on the cross block's maxima: with N == M one batch of
+ * three, otherwise three consecutive solves on the stream (otvae_sinkhorn_route tells the route of each).  batched: -1 = that rule,
+ * 0 = three consecutive solves whatever the shape, 1 = one batch of three (N == M only); the bits do not depend on it.
+ *   terms[3] (fp64) = W(z, y), W(z, z), W(y, y), unscaled, each summed in fp64 in the fixed order of otvae_ot_cost;
+ *   loss[i] = loss_scale (terms[0] - terms[1] / 2 - terms[2] / 2) for every i < N (one entry per sample, prior/base.py:74-78);
+ *   pi_zy[N][M], pi_zz[N][N]: the plans the gradient needs (fp32: 16-byte aligned);
+ *   iters[1] = max_iter, or -1 if a one-launch solve was starved: then loss, terms and both plans are NaN.
+ * A latent or draw that is not finite makes the loss NaN.  6 launches batched (cost, init, solve, finish, read-out x 2), 12 otherwise (one-launch solves).
+ * ws: otvae_sinkhorn_div_ws bytes (-1: N or M beyond 32768 or a bad argument).
+ * otvae_sinkhorn_div_grad, the envelope gradient (plans held constant, nothing for y), one launch, no atomics, no workspace:
+ *   gz[i][d] = (gadd ? gadd[i][d] : 0) + s (2 sum_j pi_zy,ij (z_id - y_jd) - sum_j (pi_zz,ij + pi_zz,ji) (z_id - z_jd)),
+ *   s = scale sum_q g[q], g[ng] the upstream gradients of the loss replicas (device memory), gadd[N][D] the gradient reaching z
+ *   through its other consumer.  fp32: the K-concatenated product [pi_zy | -(pi_zz + pi_zz^T) / 2] [y ; z] on the matrix cores, the
+ *   transposed operand read through LDS, fixed summation order. */
+int64_t otvae_sinkhorn_div_ws(int dtype, int N, int M);
+int otvae_sinkhorn_div_fwd(int dtype, const void* z, const void* y, int N, int M, int D, double reg, int max_iter, double loss_scale,
+                           int batched, void* ws, void* loss, double* terms, void* pi_zy, void* pi_zz, int32_t* iters, void* stream);
+int otvae_sinkhorn_div_grad(int dtype, const void* z, const void* y, const void* pi_zy, const void* pi_zz, const void* g, int ng,
+                            double scale, const void* gadd, int N, int M, int D, void* gz, void* stream);
+
 /* ---- sliced Wasserstein-2 between latents and prior draws (SlicedWassersteinPrior; SURVEY F3: no reference class) ------- */
 /* z[N][D], y[N][D], dirs[L][D] (raw direction draws), all fp32.  theta_l = dirs_l / |dirs_l| (written to theta[L][D]); p = z theta^T,
  * q = y theta^T; every column of p (with its row indices) and of q is sorted in LDS by a bitonic network padded with +inf to the next

@@ -153,6 +153,9 @@ SIGNATURES = {
     "otvae_sinkhorn_log_normalized": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, f64, i32, f64, vp, vp, vp, vp, vp, vp, vp]),
     "otvae_sinkhorn_prior_ws": (i64, [i32, i32, i32]),
     "otvae_sinkhorn_prior_fwd": (i32, [i32, vp, vp, i32, i32, i32, f64, i32, f64, f64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "otvae_sinkhorn_div_ws": (i64, [i32, i32, i32]),
+    "otvae_sinkhorn_div_fwd": (i32, [i32, vp, vp, i32, i32, i32, f64, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "otvae_sinkhorn_div_grad": (i32, [i32, vp, vp, vp, vp, vp, i32, f64, vp, i32, i32, i32, vp, vp]),
     "otvae_sqdist_max_parts": (i32, [i32, i32, i32]),
     "otvae_sqdist_max": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "otvae_normal_fill": (i32, [vp, i64, vp, i32, i32, vp]),

@@ -13,6 +13,7 @@
 // plan row) is in sinkhorn_rows.h, shared with the tape-recording forward of sinkhorn_diff.hip.
 #include <type_traits>
 #include "sinkhorn_rows.h"
+#include "sinkhorn_solve.h"
 
 // pi = exp(u_i + v_j + Cr_ij) in place over Cr, after the launches
 template <typename T>
@@ -438,6 +439,15 @@ extern "C" int otvae_sinkhorn_log_normalized(int dtype, const void* a, const voi
                                     (const float*)pmax, P, (float*)cmax, ws, (float*)pi, (float*)u, (float*)v, iters_done, st);
     return sinkhorn_impl<double>((const double*)a, (const double*)b, (const double*)C, nb, N, M, reg, max_iter, threshold,
                                  (const double*)pmax, P, (double*)cmax, ws, (double*)pi, (double*)u, (double*)v, iters_done, st);
+}
+
+int otvae_sk_solve_uniform(int dtype, const void* C, int nb, int N, int M, double reg, int max_iter, const void* pmax, int P, void* ws,
+                           void* pi, void* u, void* v, int32_t* iters_done, hipStream_t st) {
+    if (dtype == 0)
+        return sinkhorn_impl<float>(nullptr, nullptr, (const float*)C, nb, N, M, reg, max_iter, 0.0, (const float*)pmax, P, nullptr, ws,
+                                    (float*)pi, (float*)u, (float*)v, iters_done, st);
+    return sinkhorn_impl<double>(nullptr, nullptr, (const double*)C, nb, N, M, reg, max_iter, 0.0, (const double*)pmax, P, nullptr, ws,
+                                 (double*)pi, (double*)u, (double*)v, iters_done, st);
 }
 
 // ---- sum_ij C*pi ---------------------------------------------------------------------------------------------

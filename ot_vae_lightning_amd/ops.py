@@ -17,6 +17,8 @@ with known output shapes.  Every forward op has a ``*_backward`` op of its own; 
                                     projection)
     otvae::mmd_prior                kernel two-sample (MMD) loss and its latent  no reference class (SURVEY.md F3)
                                     gradient, one fused launch
+    otvae::sinkhorn_divergence      debiased entropic OT: W(z,y) - W(z,z)/2 -    no reference class (SURVEY.md F3); the solve is
+                                    W(y,y)/2 at one epsilon, envelope gradient   sinkhorn_log's, ot/w2_utils.py:276-319
     otvae::soft_cross_entropy       DAD.prior_loss's shifted soft-label CE       model/discrete_auto_diffuser.py:63-72
     otvae::gaussian_blur            torchvision's gaussian_blur (GaussianBlur)   tests/test_latent_transport.py:35
     otvae::ssim_loss                SSIMLoss: the per-image SSIM values [B] and  torchmetrics' ssim, differentiable
@@ -57,7 +59,7 @@ from ._lib import check, ptr, stream
 __all__ = ["OPS"]
 
 OPS = ("qkv_attention", "bn_batch_stats", "conv_bn_act", "gaussian_prior", "nelbo_loss", "sinkhorn_prior", "gaussian_w2_prior",
-       "soft_cross_entropy", "gaussian_blur", "sliced_w2", "mmd_prior", "ssim_loss", "ms_ssim")
+       "soft_cross_entropy", "gaussian_blur", "sliced_w2", "mmd_prior", "ssim_loss", "ms_ssim", "sinkhorn_divergence")
 _lib_def = torch.library.Library("otvae", "DEF")
 
 
@@ -445,6 +447,82 @@ def _sk_backward(ctx, g, _gpi, _giters):
 
 
 torch.library.register_autograd("otvae::sinkhorn_prior", _sk_backward, setup_context=_sk_setup)
+
+
+# ------------------------------------------------------------------------------------------------ Sinkhorn divergence prior
+def sinkhorn_div_check(z: Tensor, y: Tensor, reg: float, max_iter: int) -> None:
+    """the refusals of ``otvae::sinkhorn_divergence``, before any kernel (also called by ``SinkhornDivergencePrior`` and
+    ``ot.sinkhorn_divergence``)"""
+    if z.dim() != 2 or y.dim() != 2:
+        raise ValueError(f"sinkhorn_divergence takes z [N, D] and y [M, D]; got {tuple(z.shape)}, {tuple(y.shape)}")
+    if y.shape[1] != z.shape[1]:
+        raise ValueError(f"sinkhorn_divergence: prior samples are {tuple(y.shape)}, latents {tuple(z.shape)}: the widths D differ")
+    if z.shape[0] < 1 or y.shape[0] < 1 or z.shape[1] < 1:
+        raise ValueError(f"sinkhorn_divergence needs N, M, D >= 1, got N = {z.shape[0]}, M = {y.shape[0]}, D = {z.shape[1]}")
+    if not float(reg) > 0:
+        raise ValueError(f"sinkhorn_divergence: reg must be positive, got {reg!r}")
+    if int(max_iter) < 0:
+        raise ValueError(f"sinkhorn_divergence: max_iter must not be negative, got {max_iter!r}")
+    if z.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"sinkhorn_divergence computes in float32 or float64, got {z.dtype} latents")
+    _lib.require_cuda(z, "latents")
+    _lib.require_cuda(y, "prior samples")
+
+
+def _sd_fwd(z: Tensor, y: Tensor, reg: float, max_iter: int, scale: float):
+    sinkhorn_div_check(z, y, reg, max_iter)
+    lib = _lib.load()
+    z, y = z.contiguous(), y.to(z.dtype).contiguous()
+    (n, d), m = z.shape, y.shape[0]
+    dt = 0 if z.dtype == torch.float32 else 1
+    nbytes = lib.otvae_sinkhorn_div_ws(dt, n, m)
+    if nbytes < 0:
+        raise NotImplementedError(f"sinkhorn_divergence is built for N, M <= 32768, got N = {n}, M = {m}")
+    new = lambda *shape: torch.empty(shape, device=z.device, dtype=z.dtype)  # noqa: E731
+    loss, pi_zy, pi_zz = new(n), new(n, m), new(n, n)   # loss: one entry per sample
+    terms = torch.empty(3, device=z.device, dtype=torch.float64)
+    iters = torch.empty(1, device=z.device, dtype=torch.int32)
+    ws = torch.empty(nbytes, device=z.device, dtype=torch.uint8)
+    check(lib.otvae_sinkhorn_div_fwd(dt, ptr(z), ptr(y), n, m, d, float(reg), int(max_iter), float(scale), -1, ptr(ws), ptr(loss),
+                                     ptr(terms), ptr(pi_zy), ptr(pi_zz), ptr(iters), stream()), "otvae_sinkhorn_div_fwd")
+    return loss, terms, pi_zy, pi_zz, iters
+
+
+def _sd_bwd(g: Tensor, gadd: Optional[Tensor], z: Tensor, y: Tensor, pi_zy: Tensor, pi_zz: Tensor, scale: float):
+    z, y = z.contiguous(), y.to(z.dtype).contiguous()
+    n, d = z.shape
+    gz = torch.empty_like(z)
+    gadd = _dense_or_none(gadd)
+    check(_lib.load().otvae_sinkhorn_div_grad(0 if z.dtype == torch.float32 else 1, ptr(z), ptr(y), ptr(pi_zy.contiguous()),
+                                              ptr(pi_zz.contiguous()), ptr(g.to(z.dtype).contiguous()), g.numel(), float(scale), ptr(gadd),
+                                              n, y.shape[0], d, ptr(gz), stream()), "otvae_sinkhorn_div_grad")
+    return gz
+
+
+_define("sinkhorn_divergence", "(Tensor z, Tensor y, float reg, int max_iter, float scale) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
+        _sd_fwd, lambda z, y, reg, max_iter, scale: (z.new_empty(z.shape[0]), z.new_empty(3, dtype=torch.float64),
+                                                     z.new_empty(z.shape[0], y.shape[0]), z.new_empty(z.shape[0], z.shape[0]),
+                                                     z.new_empty(1, dtype=torch.int32)))
+_define("sinkhorn_divergence_backward", "(Tensor g, Tensor? gadd, Tensor z, Tensor y, Tensor pi_zy, Tensor pi_zz, float scale) -> Tensor",
+        _sd_bwd, lambda g, gadd, z, y, pi_zy, pi_zz, scale: torch.empty_like(z))
+
+
+def _sd_setup(ctx, inputs, output):
+    z, y, _, _, scale = inputs
+    ctx.save_for_backward(z, y, output[2], output[3])
+    ctx.scale = scale
+    ctx.set_materialize_grads(False)   # terms / plans / iters never carry a gradient
+
+
+def _sd_backward(ctx, g, *_):
+    if g is None:
+        return None, None, None, None, None
+    z, y, pi_zy, pi_zz = ctx.saved_tensors
+    return torch.ops.otvae.sinkhorn_divergence_backward(g, None, z, y, pi_zy, pi_zz, ctx.scale), None, None, None, None
+
+
+torch.library.register_autograd("otvae::sinkhorn_divergence", _sd_backward, setup_context=_sd_setup)
+_refuse_second_derivative("sinkhorn_divergence_backward", "Sinkhorn divergence prior")
 
 
 # ------------------------------------------------------------------------------------------------ sliced W2 prior

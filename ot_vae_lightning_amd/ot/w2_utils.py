@@ -4,7 +4,8 @@
 Out of scope for this path: GMM transport (``batch_ot_gmm``), barycenters, the stochastic
 (eq. 19) operators -- they raise ``NotImplementedError``.
 ``sliced_w2`` has no counterpart in the reference: the sliced Wasserstein-2 distance behind ``prior.SlicedWassersteinPrior``; nor
-has ``mmd2``, the kernel two-sample statistic behind ``prior.MMDPrior``."""
+has ``mmd2``, the kernel two-sample statistic behind ``prior.MMDPrior``, nor ``sinkhorn_divergence``, the debiased entropic cost behind
+``prior.SinkhornDivergencePrior``."""
 import math
 import warnings
 from functools import partial
@@ -21,6 +22,7 @@ from .matrix_utils import (STABILITY_CONST, cholesky, pinv_sym, spectral_fn, eig
                            spectral_fn)
 
 __all__ = ["w2_gaussian", "batch_w2_dissimilarity_gaussian_diag", "batch_w2_dissimilarity_gaussian", "gaussian_barycenter", "batch_ot_gmm", "sinkhorn_log", "sinkhorn_log_potentials", "sliced_w2", "mmd2",
+           "sinkhorn_divergence",
            "sq_euclidean_cost", "ot_cost", "compute_transport_operators", "apply_transport", "W2Mixin"]
 
 _DT = {torch.float32: 0, torch.float64: 1}
@@ -176,6 +178,19 @@ def mmd2(z: Tensor, y: Tensor, kernel: str = "imq", scales=(0.1, 0.2, 0.5, 1.0, 
     _lib.require_cuda(z, "z")
     need_grad = bool(torch.is_grad_enabled() and z.requires_grad)
     return torch.ops.otvae.mmd_prior(z, y.detach(), kid, list(scales), float(sigma2), bool(unbiased), 1.0, need_grad)[0][0]
+
+
+def sinkhorn_divergence(z: Tensor, y: Tensor, reg: float = 0.05, max_iter: int = 50) -> Tensor:
+    """Sinkhorn divergence between two samples: z [N, D], y [M, D] (float32 or float64, any N against any M) -> the scalar
+    W(z, y) - W(z, z) / 2 - W(y, y) / 2 with W(p, q) = sum_ij C_ij pi_ij for C_ij = |p_i - q_j|^2 and pi the entropic plan of
+    C / max C_zy (uniform marginals, exactly ``max_iter`` iterations of ``sinkhorn_log``): the three plans share one absolute epsilon
+    and one iteration count, so that the divergence of a sample against itself is zero.
+
+    Differentiable in ``z`` (``otvae::sinkhorn_divergence`` / ``otvae::sinkhorn_divergence_backward``) with the plans held constant (the
+    envelope gradient); ``y`` gets no gradient."""
+    from .. import ops
+    ops.sinkhorn_div_check(z, y, reg, max_iter)
+    return torch.ops.otvae.sinkhorn_divergence(z, y.detach(), float(reg), int(max_iter), 1.0)[0][0]
 
 
 class _SqEuclideanCostFn(torch.autograd.Function):
