@@ -959,6 +959,25 @@ int otvae_soft_ce_bwd(const float* logits, int64_t logits_stride_b, int64_t logi
  * (the draw depends on (key, col, b) only; the caller advances the counter).  ids: int64 [B][T] with row stride ids_stride. */
 int otvae_categorical_sample(const float* logits, int64_t stride_b, int64_t stride_t, int pos, int B, int K, const float* u,
                              const int64_t* key, int64_t* ids, int64_t ids_stride, int T, int col, void* stream);
+/* The same step (discrete_auto_diffuser.py:88-89, which the reference can only draw unfiltered) under a temperature, top-k and top-p
+ * (nucleus) filtering, applied in that order; otvae_categorical_sample's parameters, then:
+ *   temperature >= 0: weights w_k = exp((logits[k] - max) / temperature) in fp64; 0 decodes greedily;
+ *   top_k (0 = off): the first min(top_k, K) entries of the order (logit descending, index ascending: ties fall to the lower index) survive;
+ *   top_p in (0, 1] (1 = off): a survivor is kept iff the mass of the survivors before it in the order, over the survivors' total, is < top_p
+ *     (the smallest prefix whose mass reaches top_p; the first entry is always kept);
+ *   kept [B] (nullable): the number of kept entries per row.
+ * ids[b][col] = the inverse CDF of u[b] over the kept entries walked in index order, dropped entries weighing 0: the number of entries whose
+ * cumulative kept mass is <= u[b] * (kept total), clamped to the last kept index -- always a kept index.  temperature = 1 with both filters
+ * off gives otvae_categorical_sample's ids bit for bit, for the same u and for the same key.  temperature = 0 and top_k = 1 give the first
+ * entry of the order.  -inf logits weigh 0; rows holding NaN or nothing but -inf are outside the contract.  A kept entry of weight 0 (a -inf
+ * logit inside the top_k, or an exp that underflows) is never drawn: u = 0 yields the first kept entry of positive weight.  One launch, no
+ * host read.
+ * OTVAE_EINVAL: temperature < 0 or not finite, top_k < 0, top_p outside (0, 1].  A row is sorted in LDS when top-k or top-p takes effect:
+ * OTVAE_EUNSUPPORTED then for K > 16384 (8 bytes per entry of K rounded up to a power of two); temperature alone and greedy decoding
+ * take any K. */
+int otvae_filtered_sample(const float* logits, int64_t stride_b, int64_t stride_t, int pos, int B, int K, const float* u,
+                          const int64_t* key, int64_t* ids, int64_t ids_stride, int T, int col, float temperature, int top_k,
+                          float top_p, int32_t* kept, void* stream);
 /* The decode of sampled ids (discrete_auto_diffuser.py:92-93: one_hot(ids) @ codebook, B*T*K*d multiply-adds for a row gather):
  * out[n][:] = codebook[ids[n]][:], codebook [K][d], ids [N] int64; an id outside [0, K) yields a NaN row. */
 int otvae_codebook_gather(const float* codebook, const int64_t* ids, int64_t N, int K, int d, float* out, void* stream);

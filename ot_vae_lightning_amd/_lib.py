@@ -226,6 +226,7 @@ SIGNATURES = {
     "otvae_soft_ce_fwd": (i32, [vp, i64, i64, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp]),
     "otvae_soft_ce_bwd": (i32, [vp, i64, i64, vp, i64, i64, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "otvae_categorical_sample": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, i64, i32, i32, vp]),
+    "otvae_filtered_sample": (i32, [vp, i64, i64, i32, i32, i32, vp, vp, vp, i64, i32, i32, f32, i32, f32, vp, vp]),
     "otvae_codebook_gather": (i32, [vp, vp, i64, i32, i32, vp, vp]),
     "otvae_ar_layer_step": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp]),
     "otvae_ar_embed_step": (i32, [vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, vp, vp]),

@@ -36,9 +36,10 @@ int otvae_current_device();  // the calling thread's current HIP device, -1 when
 int otvae_cu_count();        // CUs of the current device, asked once per device (every call beyond the table); 1 when the query fails
 
 // A launch with more than 64 KiB of dynamic LDS has to be granted first, and HIP keeps that attribute per function AND per device.
-// need: bytes this launch asks for; most: what to request when a grant is needed (the kernel's widest supported shape).
+// need: bytes this launch asks for; most: what to request when a grant is needed (the kernel's widest supported shape).  A kernel whose
+// static LDS matters next to 64 KiB of dynamic LDS (dad.hip) counts it into both.
 // Users: conv_tile.hip (one-job and pair kernels), conv_wtile.hip, attention.hip (stage forward / backward), mmd.hip, mvn.hip,
-// ar_decode.hip, eigh_onesided.hip (hj_sweep_kernel, hjg_round_kernel), gaussian_ot.hip (eigh_kernel).
+// ar_decode.hip, dad.hip (filtered_sample_kernel), eigh_onesided.hip (hj_sweep_kernel, hjg_round_kernel), gaussian_ot.hip (eigh_kernel).
 template <auto Kernel>
 static int otvae_lds_grant(const char* who, size_t need, size_t most) {
     if (need <= 64 * 1024) return OTVAE_OK;

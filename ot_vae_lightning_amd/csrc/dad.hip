@@ -1,5 +1,6 @@
 // Discrete Auto Diffuser (reference model/discrete_auto_diffuser.py:56-95): the shifted soft-label cross-entropy of its training loss,
-// one categorical draw of its sampling loop, and the row gather that decodes the sampled ids.
+// one categorical draw of its sampling loop -- plain, or under a temperature, top-k and top-p (nucleus) filtering --, and the row gather
+// that decodes the sampled ids.
 //
 // soft CE.  ce[b] = sum_{t < T-1} ( -sum_k p[b][t+1][k] * log_softmax(l[b][t][:])[k] ).  The reference forms it from two sliced copies,
 // two transposes, log_softmax, a product and a sum; here a row (b, t) is ONE pass over l[b][t][:] and p[b][t+1][:]: with the running
@@ -9,6 +10,7 @@
 // Rows of up to SOFT_CE_WAVE_K entries are taken by one wave (four rows per workgroup), longer ones by a whole workgroup.
 #include "common.h"
 #include "dropout_hash.h"
+#include "ordered_key.h"
 
 #define SOFT_CE_WAVE_K 512
 
@@ -248,25 +250,42 @@ extern "C" int otvae_soft_ce_bwd(const float* logits, int64_t logits_stride_b, i
 // Thread t owns the contiguous chunk [t * C, (t + 1) * C) of the row, C = ceil(K / 256): chunk sums in index order, the 256 chunk totals
 // scanned in index order by one thread, then every thread walks its chunk again from its prefix and counts the entries whose cumulative
 // sum is <= u * total.  The cumulative sums are non-decreasing, so the counts add up to the index.  exp and the scan are fp64.
-__global__ __launch_bounds__(256) void categorical_sample_kernel(const float* __restrict__ logits, int64_t sb, int64_t pos_off, int K,
-                                                                 const float* __restrict__ u, const int64_t* __restrict__ key, int B,
-                                                                 int64_t* __restrict__ ids, int64_t ids_stride, int col) {
+//
+// The filtered draw (otvae_filtered_sample) runs the same walk over other weights.  Entries are totally ordered by (logit descending,
+// index ascending); as ONE unsigned number that order is the packed key (ord_f32(logit) << 32) | (0xFFFFFFFF - index), all keys of a row
+// distinct.  SCALE: the weight is exp((l - m) / tau).  CUT: an entry takes part iff its packed key is >= `cut`, the key of the last entry
+// the filters keep; the others weigh 0, and the clamp is to the last kept index instead of K - 1.
+__device__ __forceinline__ unsigned long long packed_key(float l, int k) {
+    return ((unsigned long long)ord_f32(l + 0.f) << 32) | (0xFFFFFFFFu - (unsigned)k);   // + 0.f: -0 and +0 tie
+}
+
+template <bool SCALE, bool CUT>
+__device__ __forceinline__ double draw_weight(float l, int k, float m, double tau, unsigned long long cut) {
+    if (CUT && packed_key(l, k) < cut) return 0.0;
+    const double d = (double)l - (double)m;
+    return exp(SCALE ? d / tau : d);
+}
+
+__device__ __forceinline__ float block_max_256(float m, float* s_max) {   // s_max: LDS, 4 entries; ends behind a block barrier
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = m;
+    __syncthreads();
+    return fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+}
+
+// ids[b][col] = the inverse CDF of this row's uniform over the weights of l[0 .. K), m = the row's maximum.  Whole 256-thread block.
+template <bool SCALE, bool CUT>
+__device__ __forceinline__ void inverse_cdf_walk(const float* __restrict__ l, int K, float m, double tau, unsigned long long cut,
+                                                 const float* __restrict__ u, const int64_t* __restrict__ key, int B, int b,
+                                                 int64_t* __restrict__ ids, int64_t ids_stride, int col) {
     __shared__ double s_sum[256];
     __shared__ double s_target;
-    __shared__ float s_max[4];
-    __shared__ int s_cnt[4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* __restrict__ l = logits + b * sb + pos_off;
-    float m = -INFINITY;
-    for (int k = tid; k < K; k += 256) m = fmaxf(m, l[k]);
-    m = wave_max(m);
-    if ((tid & 63) == 0) s_max[tid >> 6] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+    __shared__ int s_cnt[4], s_last[4];
+    const int tid = threadIdx.x;
     const int C = (K + 255) / 256;
     const int k0 = tid * C < K ? tid * C : K, k1 = k0 + C < K ? k0 + C : K;
     double c = 0.0;
-    for (int k = k0; k < k1; ++k) c += exp((double)l[k] - (double)m);
+    for (int k = k0; k < k1; ++k) c += draw_weight<SCALE, CUT>(l[k], k, m, tau, cut);
     s_sum[tid] = c;
     __syncthreads();
     if (tid == 0) {
@@ -289,35 +308,211 @@ __global__ __launch_bounds__(256) void categorical_sample_kernel(const float* __
     __syncthreads();
     const double target = s_target;
     double run = s_sum[tid];
-    int cnt = 0;
+    int cnt = 0, last = CUT ? -1 : K - 1;
     for (int k = k0; k < k1; ++k) {
-        run += exp((double)l[k] - (double)m);
+        const float lk = l[k];
+        run += draw_weight<SCALE, CUT>(lk, k, m, tau, cut);
         cnt += run <= target ? 1 : 0;
+        if (CUT && packed_key(lk, k) >= cut) last = k;
     }
     cnt = wave_sum(cnt);
+    if (CUT) last = wave_max(last);
     __syncthreads();
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+    if ((tid & 63) == 0) {
+        s_cnt[tid >> 6] = cnt;
+        s_last[tid >> 6] = last;
+    }
     __syncthreads();
     if (tid == 0) {
         const int idx = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        ids[b * ids_stride + col] = idx < K - 1 ? idx : K - 1;
+        if (CUT) last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
+        ids[b * ids_stride + col] = idx < last ? idx : last;
     }
+}
+
+__global__ __launch_bounds__(256) void categorical_sample_kernel(const float* __restrict__ logits, int64_t sb, int64_t pos_off, int K,
+                                                                 const float* __restrict__ u, const int64_t* __restrict__ key, int B,
+                                                                 int64_t* __restrict__ ids, int64_t ids_stride, int col) {
+    __shared__ float s_max[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ l = logits + b * sb + pos_off;
+    float m = -INFINITY;
+    for (int k = tid; k < K; k += 256) m = fmaxf(m, l[k]);
+    m = block_max_256(m, s_max);
+    inverse_cdf_walk<false, false>(l, K, m, 1.0, 0ULL, u, key, B, b, ids, ids_stride, col);
+}
+
+// the same draw with weights exp((l - m) / temperature): what otvae_filtered_sample launches when neither top-k nor top-p takes effect
+__global__ __launch_bounds__(256) void scaled_sample_kernel(const float* __restrict__ logits, int64_t sb, int64_t pos_off, int K,
+                                                            const float* __restrict__ u, const int64_t* __restrict__ key, int B,
+                                                            int64_t* __restrict__ ids, int64_t ids_stride, int col, float temperature,
+                                                            int32_t* __restrict__ kept) {
+    __shared__ float s_max[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ l = logits + b * sb + pos_off;
+    float m = -INFINITY;
+    for (int k = tid; k < K; k += 256) m = fmaxf(m, l[k]);
+    m = block_max_256(m, s_max);
+    if (tid == 0 && kept) kept[b] = K;
+    inverse_cdf_walk<true, false>(l, K, m, (double)temperature, 0ULL, u, key, B, b, ids, ids_stride, col);
+}
+
+// ---- the filtered draw: temperature, then top-k, then top-p on the renormalised survivors ---------------------------------------------
+// The row's packed keys go into LDS (8 P bytes, P = K rounded up to a power of two; the padding keys are 0, below every real key)
+// and one descending bitonic network turns them into the order; steps of distance <= 64 stay inside a wave's own 128-key chunks
+// (sliced_w2.hip).  The first kk = min(top_k, K) sorted entries survive top-k; their fp64 weights are summed in 256 contiguous chunks of
+// the order, the chunk totals scanned by one thread, and entry j survives top-p iff (mass before j) / (mass of the kk) < top_p -- a prefix
+// of r entries.  The key at rank r - 1 is the cut of the index-order walk above.  The chunk length is odd: consecutive lanes then read
+// 64-bit words an odd number of words apart, which no two lanes of a 32-lane group map to one LDS bank.
+#define FS_MAX_K 16384
+#define FS_STATIC_LDS 4608   // the kernel's static LDS (scan scratch here and in the walk: 4176 bytes by the compiler's report), rounded up
+
+__global__ __launch_bounds__(256) void filtered_sample_kernel(const float* __restrict__ logits, int64_t sb, int64_t pos_off, int K, int P,
+                                                              const float* __restrict__ u, const int64_t* __restrict__ key, int B,
+                                                              int64_t* __restrict__ ids, int64_t ids_stride, int col, float temperature,
+                                                              int top_k, float top_p, int32_t* __restrict__ kept) {
+    extern __shared__ __align__(16) unsigned long long fs_keys[];   // [P]
+    __shared__ double s_part[256];
+    __shared__ double s_total;
+    __shared__ int s_cnt[4];
+    __shared__ unsigned long long s_cut;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ l = logits + b * sb + pos_off;
+    const double tau = (double)temperature;
+    for (int k = tid; k < P; k += 256) fs_keys[k] = k < K ? packed_key(l[k], k) : 0ULL;
+    __syncthreads();
+    const int half = P >> 1;
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < half; t += 256) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int hi = lo | j;
+                const bool down = (lo & k) == 0;
+                const unsigned long long a = fs_keys[lo], c = fs_keys[hi];
+                const bool swap = (a < c) == down;   // both loads first, stores without a branch
+                fs_keys[lo] = swap ? c : a;
+                fs_keys[hi] = swap ? a : c;
+            }
+            const int jn = j > 1 ? j >> 1 : k;   // the next step's distance
+            if (j > 64 || jn > 64) __syncthreads();
+            else wave_lds_sync();
+        }
+    }
+    __syncthreads();
+    const float m = unord_f32((unsigned)(fs_keys[0] >> 32));   // the first of the order holds the row's maximum
+    const int kk = top_k > 0 && top_k < K ? top_k : K;
+    int r = kk;
+    if (top_p < 1.f) {
+        const int C = ((kk + 255) / 256) | 1;
+        const int j0 = tid * C < kk ? tid * C : kk, j1 = j0 + C < kk ? j0 + C : kk;
+        double c = 0.0;
+        for (int j = j0; j < j1; ++j) c += exp(((double)unord_f32((unsigned)(fs_keys[j] >> 32)) - (double)m) / tau);
+        s_part[tid] = c;
+        __syncthreads();
+        if (tid == 0) {
+            double run = 0.0;
+            for (int i = 0; i < 256; ++i) {
+                const double v = s_part[i];
+                s_part[i] = run;   // exclusive prefix
+                run += v;
+            }
+            s_total = run;
+        }
+        __syncthreads();
+        const double total = s_total, p = (double)top_p;
+        double run = s_part[tid];
+        int cnt = 0;
+        for (int j = j0; j < j1; ++j) {
+            cnt += run / total < p ? 1 : 0;
+            run += exp(((double)unord_f32((unsigned)(fs_keys[j] >> 32)) - (double)m) / tau);
+        }
+        cnt = wave_sum(cnt);
+        if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+        __syncthreads();
+        r = max(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3], 1);   // the first entry is always kept
+    }
+    if (tid == 0) {
+        s_cut = fs_keys[r - 1];
+        if (kept) kept[b] = r;
+    }
+    __syncthreads();
+    inverse_cdf_walk<true, true>(l, K, m, tau, s_cut, u, key, B, b, ids, ids_stride, col);
+}
+
+// temperature 0, or top_k = 1: the first entry of the order, i.e. the largest packed key of the row.  No limit on K.
+__global__ __launch_bounds__(256) void greedy_sample_kernel(const float* __restrict__ logits, int64_t sb, int64_t pos_off, int K,
+                                                            int64_t* __restrict__ ids, int64_t ids_stride, int col,
+                                                            int32_t* __restrict__ kept) {
+    __shared__ unsigned long long s_best[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* __restrict__ l = logits + b * sb + pos_off;
+    unsigned long long best = 0ULL;
+    for (int k = tid; k < K; k += 256) {
+        const unsigned long long e = packed_key(l[k], k);
+        best = e > best ? e : best;
+    }
+    best = wave_max(best);
+    if ((tid & 63) == 0) s_best[tid >> 6] = best;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) best = s_best[w] > best ? s_best[w] : best;
+        ids[b * ids_stride + col] = (int64_t)(0xFFFFFFFFu - (unsigned)best);
+        if (kept) kept[b] = 1;
+    }
+}
+
+static int sample_check(const char* who, const float* logits, int64_t stride_b, int64_t stride_t, int pos, int B, int K, const float* u,
+                        const int64_t* key, const int64_t* ids, int64_t ids_stride, int T, int col) {
+    OTVAE_REQUIRE(logits && ids && B > 0 && (u || key), "%s: bad argument (uniforms or a generator key are required)", who);
+    if (K < 1) {
+        otvae_set_error("%s: needs at least one class (K = %d)", who, K);
+        return OTVAE_EUNSUPPORTED;
+    }
+    OTVAE_REQUIRE(pos >= 0 && stride_t >= 0 && stride_b >= 0, "%s: position %d / strides (%lld, %lld) do not address a row of %d logits", who,
+                  pos, (long long)stride_b, (long long)stride_t, K);
+    OTVAE_REQUIRE(T >= 1 && col >= 0 && col < T && ids_stride >= T, "%s: column %d outside the [%d][%d] id matrix (row stride %lld)", who, col, B,
+                  T, (long long)ids_stride);
+    return OTVAE_OK;
 }
 
 extern "C" int otvae_categorical_sample(const float* logits, int64_t stride_b, int64_t stride_t, int pos, int B, int K, const float* u,
                                         const int64_t* key, int64_t* ids, int64_t ids_stride, int T, int col, void* stream) {
-    OTVAE_REQUIRE(logits && ids && B > 0 && (u || key), "otvae_categorical_sample: bad argument (uniforms or a generator key are required)");
-    if (K < 1) {
-        otvae_set_error("otvae_categorical_sample: needs at least one class (K = %d)", K);
-        return OTVAE_EUNSUPPORTED;
-    }
-    OTVAE_REQUIRE(pos >= 0 && stride_t >= 0 && stride_b >= 0, "otvae_categorical_sample: position %d / strides (%lld, %lld) do not address a row "
-                  "of %d logits", pos, (long long)stride_b, (long long)stride_t, K);
-    OTVAE_REQUIRE(T >= 1 && col >= 0 && col < T && ids_stride >= T, "otvae_categorical_sample: column %d outside the [%d][%d] id matrix (row stride %lld)",
-                  col, B, T, (long long)ids_stride);
+    if (int rc = sample_check("otvae_categorical_sample", logits, stride_b, stride_t, pos, B, K, u, key, ids, ids_stride, T, col)) return rc;
     categorical_sample_kernel<<<B, 256, 0, (hipStream_t)stream>>>(logits, stride_b, (int64_t)pos * stride_t, K, u, key, B, ids,
                                                                                 ids_stride, col);
     OTVAE_CHECK_LAUNCH("otvae_categorical_sample");
+    return OTVAE_OK;
+}
+
+extern "C" int otvae_filtered_sample(const float* logits, int64_t stride_b, int64_t stride_t, int pos, int B, int K, const float* u,
+                                     const int64_t* key, int64_t* ids, int64_t ids_stride, int T, int col, float temperature, int top_k,
+                                     float top_p, int32_t* kept, void* stream) {
+    const char* who = "otvae_filtered_sample";
+    if (int rc = sample_check(who, logits, stride_b, stride_t, pos, B, K, u, key, ids, ids_stride, T, col)) return rc;
+    OTVAE_REQUIRE(temperature >= 0.f && temperature <= 3.402823466e38f, "%s: temperature %g is not a finite number >= 0", who,
+                  (double)temperature);
+    OTVAE_REQUIRE(top_k >= 0, "%s: top_k = %d is negative (0 switches it off)", who, top_k);
+    OTVAE_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p = %g is outside (0, 1] (1 switches it off)", who, (double)top_p);
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t pos_off = (int64_t)pos * stride_t;
+    if (temperature == 0.f || top_k == 1) {
+        greedy_sample_kernel<<<B, 256, 0, st>>>(logits, stride_b, pos_off, K, ids, ids_stride, col, kept);
+    } else if ((top_k == 0 || top_k >= K) && top_p == 1.f) {
+        scaled_sample_kernel<<<B, 256, 0, st>>>(logits, stride_b, pos_off, K, u, key, B, ids, ids_stride, col, temperature, kept);
+    } else {
+        if (K > FS_MAX_K) {
+            otvae_set_error("%s: top-k / top-p filtering sorts the row in LDS: K = %d is beyond the limit of %d", who, K, FS_MAX_K);
+            return OTVAE_EUNSUPPORTED;
+        }
+        int P = 1;
+        while (P < K) P <<= 1;
+        const size_t lds = (size_t)P * sizeof(unsigned long long);
+        // static LDS counted in: at P = 8192 the keys alone fill 64 KiB and the scan scratch comes on top
+        if (int rc = otvae_lds_grant<&filtered_sample_kernel>(who, lds + FS_STATIC_LDS, (size_t)FS_MAX_K * 8 + FS_STATIC_LDS)) return rc;
+        filtered_sample_kernel<<<B, 256, lds, st>>>(logits, stride_b, pos_off, K, P, u, key, B, ids, ids_stride, col, temperature, top_k,
+                                                          top_p, kept);
+    }
+    OTVAE_CHECK_LAUNCH(who);
     return OTVAE_OK;
 }
 

@@ -19,24 +19,10 @@
 // Backward: gz = gadd + c * resid^T theta on the matrix cores (16 x 16 x 4 fp32 MFMA, one wave per 16 x 16 tile of gz, both operands
 // read straight from global memory: resid is [L][N], i.e. already K-major, and theta is [L][D]), one launch.
 #include "common.h"
+#include "ordered_key.h"
 
 #define SW_MAX_N 4096
 #define SW_LANES_PER_ROW 8
-
-__device__ __forceinline__ unsigned sw_ord(float f) {  // order-preserving float -> unsigned
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sw_unord(unsigned o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
-// orders this wave's LDS accesses across a step of the network that no other wave takes part in (compiler fence + wave barrier)
-__device__ __forceinline__ void sw_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // block-wide sum in a fixed order (lane tree, then the waves in index order); every thread gets the total.  red: LDS, 16 entries
 template <typename T>
@@ -73,7 +59,7 @@ sliced_w2_fwd_kernel(const float* __restrict__ z, const float* __restrict__ y, c
 
     // 2. + 3. projections and keys
     const int s = tid & (SW_LANES_PER_ROW - 1), slot = tid / SW_LANES_PER_ROW, slots = T / SW_LANES_PER_ROW;
-    const unsigned ord_inf = sw_ord(__uint_as_float(0x7f800000u));
+    const unsigned ord_inf = ord_f32(__uint_as_float(0x7f800000u));
     for (int base = 0; base < N; base += slots) {   // block-uniform trip count: the lane exchanges below are never divergent
         const int i = base + slot;
         const bool live = i < N;
@@ -112,8 +98,8 @@ sliced_w2_fwd_kernel(const float* __restrict__ z, const float* __restrict__ y, c
             ay += 0.f;
             const bool fz = isfinite(az), fy = isfinite(ay);
             if (!(fz && fy)) atomicOr(&s_bad, 1);
-            zk[i] = ((unsigned long long)(fz ? sw_ord(az) : ord_inf) << 32) | (unsigned)i;
-            yk[i] = fy ? sw_ord(ay) : ord_inf;
+            zk[i] = ((unsigned long long)(fz ? ord_f32(az) : ord_inf) << 32) | (unsigned)i;
+            yk[i] = fy ? ord_f32(ay) : ord_inf;
         }
     }
     for (int i = N + tid; i < P; i += T) {   // padding: +inf behind every real row
@@ -142,7 +128,7 @@ sliced_w2_fwd_kernel(const float* __restrict__ z, const float* __restrict__ y, c
             // wave's own LDS accesses, which complete in issue order, are all that has to be ordered
             const int jn = j > 1 ? j >> 1 : k;   // the next step's distance
             if (j > 64 || jn > 64) __syncthreads();
-            else sw_wave_sync();
+            else wave_lds_sync();
         }
     }
     __syncthreads();
@@ -154,7 +140,7 @@ sliced_w2_fwd_kernel(const float* __restrict__ z, const float* __restrict__ y, c
     for (int k = tid; k < N; k += T) {
         const unsigned long long e = zk[k];
         const unsigned row = (unsigned)e;
-        const float r = sw_unord((unsigned)(e >> 32)) - sw_unord(yk[k]);
+        const float r = unord_f32((unsigned)(e >> 32)) - unord_f32(yk[k]);
         if (row < (unsigned)N) resid[l * N + row] = bad ? nanf_ : r;   // (always true: the real rows are the first N)
         acc += (double)r * (double)r;
     }

@@ -2132,12 +2132,31 @@ def soft_cross_entropy(logits: Tensor, probs: Tensor) -> Tensor:
     return torch.ops.otvae.soft_cross_entropy(logits, probs)[0]
 
 
+def check_token_filter(temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None) -> bool:
+    """Validates the scalars of a filtered draw (``ValueError``); True when they differ from the plain draw's defaults."""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or temperature < 0:
+        raise ValueError(f"`temperature` must be a finite number >= 0 (0 decodes greedily), got {temperature!r}")
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 1):
+        raise ValueError(f"`top_k` must be None or an integer >= 1, got {top_k!r}")
+    if top_p is not None and (isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1):
+        raise ValueError(f"`top_p` must be None or lie in (0, 1], got {top_p!r}")
+    return temperature != 1.0 or top_k is not None or top_p is not None
+
+
 @torch.no_grad()
 def categorical_sample_(ids: Tensor, col: int, logits: Tensor, pos: int, u: Optional[Tensor] = None,
-                        key: Optional[Tensor] = None) -> Tensor:
+                        key: Optional[Tensor] = None, *, temperature: float = 1.0, top_k: Optional[int] = None,
+                        top_p: Optional[float] = None, kept: Optional[Tensor] = None) -> Tensor:
     """``ids[:, col] = Categorical(logits[:, pos].softmax(-1)).sample()`` in place (reference model/discrete_auto_diffuser.py:88-89) as
     the inverse CDF of one uniform per row: ``u`` [B] in [0, 1), or drawn on the device from ``key`` (``new_dropout_key``: int64
-    {seed, call counter}; the draw depends on (key, col, row) only).  ids: int64 [B, T]; logits: float32 [B, *, K].  No host read."""
+    {seed, call counter}; the draw depends on (key, col, row) only).  ids: int64 [B, T]; logits: float32 [B, *, K].  No host read.
+
+    ``temperature``, ``top_k`` and ``top_p`` filter the distribution first, in that order (``otvae_filtered_sample``): the weights are
+    ``exp((l - max) / temperature)``; the ``top_k`` largest entries survive (ties towards the lower index); of those, the smallest prefix
+    whose renormalised mass reaches ``top_p`` is kept; the uniform's inverse CDF then runs over the kept entries in index order.
+    ``temperature=0`` and ``top_k=1`` decode greedily.  ``kept``: int32 [B], receives the number of kept entries per row.  top-k / top-p
+    take rows of up to 16384 logits (``NotImplementedError`` beyond); at the defaults the call is the plain draw, unchanged."""
+    filtered = check_token_filter(temperature, top_k, top_p) or kept is not None
     _lib.require_cuda(logits, "logits")
     if ids.dim() != 2 or ids.dtype != torch.int64 or ids.stride(1) != 1:
         raise ValueError("categorical_sample_ writes into an int64 [B, T] id matrix with unit column stride")
@@ -2154,8 +2173,15 @@ def categorical_sample_(ids: Tensor, col: int, logits: Tensor, pos: int, u: Opti
         if u.shape != (ids.shape[0],):
             raise ValueError(f"`u` must hold one uniform per row ({ids.shape[0]}), got {tuple(u.shape)}")
     b, t = ids.shape
-    check(_lib.load().otvae_categorical_sample(ptr(logits), logits.stride(0), logits.stride(1), int(pos), b, logits.shape[2], ptr(u),
-                                               ptr(key), ptr(ids), ids.stride(0), t, int(col), stream()), "otvae_categorical_sample")
+    if not filtered:
+        check(_lib.load().otvae_categorical_sample(ptr(logits), logits.stride(0), logits.stride(1), int(pos), b, logits.shape[2], ptr(u),
+                                                   ptr(key), ptr(ids), ids.stride(0), t, int(col), stream()), "otvae_categorical_sample")
+        return ids
+    if kept is not None and (kept.dtype != torch.int32 or kept.shape != (b,) or not kept.is_contiguous()):
+        raise ValueError(f"`kept` must be a contiguous int32 [{b}] tensor, got {tuple(kept.shape)} {kept.dtype}")
+    check(_lib.load().otvae_filtered_sample(ptr(logits), logits.stride(0), logits.stride(1), int(pos), b, logits.shape[2], ptr(u), ptr(key),
+                                            ptr(ids), ids.stride(0), t, int(col), float(temperature), 0 if top_k is None else min(int(top_k), 2 ** 31 - 1),
+                                            1.0 if top_p is None else float(top_p), ptr(kept), stream()), "otvae_filtered_sample")
     return ids
 
 

@@ -5,7 +5,8 @@ token by token.
 
 MI355X path: the cross-entropy is one fused operator (``torch.ops.otvae.soft_cross_entropy``: one pass over the two [B, T, K]
 tensors, the one-token shift as index arithmetic), every step of the sampling loop is one launch that writes ``ids[:, i + 1]`` in
-place (``otvae_categorical_sample``: no host read inside the loop), and the sampled ids are decoded by a row gather
+place (``otvae_categorical_sample``, or ``otvae_filtered_sample`` under a temperature / top-k / top-p: no host read inside the loop),
+and the sampled ids are decoded by a row gather
 (``otvae_codebook_gather``) instead of ``one_hot @ codebook``.
 
 Deliberate difference from the reference: ``optim_parameters()`` also yields the autoregressive decoder's parameters.  The reference
@@ -57,14 +58,21 @@ class DAD(VAE):
 
     @VAE.postprocess
     def sample(self, batch_size: int, *, init_indices: Optional[Tensor] = None, noise: Optional[Tensor] = None, cached: bool = False,
-               **kwargs) -> Tensor:
+               temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None, **kwargs) -> Tensor:
         """Reference discrete_auto_diffuser.py:77-95.  ``init_indices`` (int64 [B, T], the uniformly random start; only column 0
         survives) and ``noise`` ([B, T - 1] uniforms in [0, 1): token i + 1 is the inverse CDF of ``noise[:, i]`` under the decoder's
         distribution at position i) make the draw reproducible; without them both are drawn on the device.
 
+        ``temperature``, ``top_k`` and ``top_p`` filter the decoder's distribution at every position, in that order, inside the draw's
+        one launch (``HF.categorical_sample_``): logits over ``temperature``, then the ``top_k`` most likely tokens, then of those the
+        smallest set whose renormalised mass reaches ``top_p``; ``noise[:, i]`` is then the uniform of step i under the filtered
+        distribution.  ``temperature=0`` (or ``top_k=1``) decodes greedily.  The defaults draw from the unfiltered distribution, as the
+        reference does.  top-k / top-p need ``num_embeddings <= 16384`` (``NotImplementedError`` beyond).
+
         ``cached=True`` advances the decoder one token at a time on per-layer key / value caches (``AutoRegressive.decode_state`` /
         ``step``) instead of running it on the whole id matrix T - 1 times: same draws, same distribution at every position.  A decoder
         that route cannot take (``decode_state``'s rules) raises ``NotImplementedError``; there is no silent fall-back."""
+        HF.check_token_filter(temperature, top_k, top_p)
         device, T = self.device, self.n_tokens
         state = None
         if cached:
@@ -93,7 +101,8 @@ class DAD(VAE):
                     logits, at = self.autoregressive_decoder.step(embed_ind[:, i], state).unsqueeze(1), 0
                 else:
                     logits, at = self.autoregressive_decoder(embed_ind), i
-                HF.categorical_sample_(embed_ind, i + 1, logits, at, u=None if noise is None else noise[i], key=key)
+                HF.categorical_sample_(embed_ind, i + 1, logits, at, u=None if noise is None else noise[i], key=key,
+                                       temperature=temperature, top_k=top_k, top_p=top_p)
             codebook = self.prior.codebook_model.codebook
             latents = HF.codebook_gather(codebook.reshape(-1, codebook.shape[-1]).float(), embed_ind).type_as(codebook)
         latents = self.prior.unflatten_and_unpermute(latents.transpose(0, 1))
